@@ -19,9 +19,15 @@ crosses GPUs. The timed region includes it.
 processes itself (torch.distributed.run, before this process touches the
 GPU) and exits with their status; under torchrun WORLD_SIZE must equal N.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with
-`roofline` for the closest-hit traversal kernel and `cpu_baseline` (the
-oracle/ CPU restatement on a bounded sample, N=1 only).
+Prints ONE JSON line on rank 0. A plain run
+sets up, warms up, times `--steps` steps and prints the headline fields
+(`metric`, `value`, `unit`, `ms_per_step`, ...). `--dump-outputs DIR` also
+writes the film of the last timed step to DIR/film.npy (scene, seeds and
+sample ranges are fixed, so two builds can be compared film for film).
+`--full` adds what takes runs of its own: `roofline` for the closest-hit
+traversal kernel and `kernels` (one extra, untimed counter step plus the
+committed PMC profiles) and `cpu_baseline` (the oracle/ CPU restatement on a
+bounded sample, N=1 only).
 
 The roofline names the unit that bounds the traversal: its vector-memory
 address path (TA/TCP, "vmem"). The achieved rate is the algorithmic bytes
@@ -90,8 +96,42 @@ def parse():
                    help="N>1 ranks: nccl (RCCL, the measurement) or gloo (host-staged device tensors; lets "
                         "several ranks share one GPU in a rehearsal of the N>1 code path)")
     p.add_argument("--master-port", type=int, default=29517, help="rendezvous port when bench.py starts the ranks")
-    p.add_argument("--dump-film", default="", help="save rank 0's combined film of the seed-0 step (.npy; tests)")
-    return p.parse_args()
+    p.add_argument("--dump-film", default="", help="save rank 0's combined film of the seed-0 step (.npy; tests; "
+                                                   "needs --full, whose counter step renders it)")
+    p.add_argument("--full", action="store_true",
+                   help="path_mis: after the timed steps also run the untimed counter step and the CPU baseline and "
+                        "add `roofline`, `kernels` and `cpu_baseline` to the JSON line (off: headline fields only)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="path_mis: write the film of the last timed step (rank 0's combined film, what "
+                        "render_film's caller receives) to DIR/film.npy as float32")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    if args.dump_film and not args.full:
+        p.error("--dump-film saves the film of the counter step: add --full")
+    if args.dump_outputs and args.workload != "path_mis":
+        p.error("--dump-outputs is implemented for --workload path_mis")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(film, directory):
+    """Write the film (H+2, W+2, 4) of the last timed step as
+    directory/film.npy (float32). A film above DUMP_LIMIT_BYTES is cut to a
+    fixed, seeded choice of its rows, whose indices go to film_rows.npy."""
+    import numpy as np
+
+    a = np.ascontiguousarray(film.detach().cpu().numpy(), dtype=np.float32)
+    os.makedirs(directory, exist_ok=True)
+    row_bytes = a[0].nbytes
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - 8 * a.shape[0]) // row_bytes)
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+        np.save(os.path.join(directory, "film_rows.npy"), rows.astype(np.float64))
+        a = np.ascontiguousarray(a[rows])
+    np.save(os.path.join(directory, "film.npy"), a)
 
 
 def spawn_ranks(args) -> int:
@@ -248,7 +288,7 @@ def main():
     t0 = time.perf_counter()
     agg = None
     for i in range(args.steps):
-        st = step(i, stats=True)
+        st = step(i, stats=True)  # event times on in plain and --full runs alike: both time the same step
         agg = dict(st) if agg is None else {k: agg[k] + v for k, v in st.items()}
     torch.cuda.synchronize()
     if world > 1:
@@ -259,6 +299,42 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local}" if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(combined[0], args.dump_outputs)
+
+    value = W * H * spp * args.steps / elapsed / 1e6
+    K = args.steps
+    head = {
+        "metric": "Mpaths/sec on bedroom@1280×720 spp=256, 1/2/4/8 GPUs; HBM GB/s vs peak",
+        "value": round(value, 3),
+        "unit": "Mpaths/s",
+        "n_gpus": dist.get_world_size() if world > 1 else 1,
+        "steps": K,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / K * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic: deterministic bedroom proxy (scene.xml camera/BSDFs/emitters, "
+                f"{sc.n_tris} procedural triangles)",
+        "config": {
+            "workload": f"path-mis.py NEE+MIS (BASELINE configs[1]) on bedroom-proxy {W}x{H}, global spp={spp} "
+                        f"split over {world} rank(s) by sample range, max_depth={args.max_depth}, "
+                        f"rr_depth={args.rr_depth}",
+            "global_spp": spp,
+            "spp_per_rank": s1 - s0,
+            "paths_per_step": W * H * spp,
+            "parallelism": f"sample-range shards x{world}" + (", RCCL slice-reduce of films to rank 0" if world > 1 else ""),
+        },
+    }
+    if not args.full:
+        # the plain run ends here: no counter step, PMC lookup or CPU baseline
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # visit counters (deterministic): one untimed step, same seed as step 0
     cnt = step(0, stats=True, counters=True)
     if args.dump_film and rank == 0:
@@ -266,8 +342,6 @@ def main():
 
         np.save(args.dump_film, combined[0].cpu().numpy())
 
-    value = W * H * spp * args.steps / elapsed / 1e6
-    K = args.steps
     # rank-local per-step figures (this rank's launches)
     alg_closest = (cnt["rays_closest"] * (RAY_BYTES + HIT_BYTES) + cnt["nodes_closest"] * NODE_BYTES
                    + cnt["tris_closest"] * TRI_BYTES)
@@ -315,28 +389,7 @@ def main():
         largest = {"kernel": big, "ms_per_step": kernels[big]["ms_per_step"], "bound": kernels[big].get("alg_bound"),
                    "alg_frac": kernels[big].get("alg_frac"), "hbm_frac": kernels[big].get("hbm_frac")}
         out = {
-            "metric": "Mpaths/sec on bedroom@1280×720 spp=256, 1/2/4/8 GPUs; HBM GB/s vs peak",
-            "value": round(value, 3),
-            "unit": "Mpaths/s",
-            "n_gpus": dist.get_world_size() if world > 1 else 1,
-            "steps": K,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / K * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic: deterministic bedroom proxy (scene.xml camera/BSDFs/emitters, "
-                    f"{sc.n_tris} procedural triangles)",
-            "config": {
-                "workload": f"path-mis.py NEE+MIS (BASELINE configs[1]) on bedroom-proxy {W}x{H}, global spp={spp} "
-                            f"split over {world} rank(s) by sample range, max_depth={args.max_depth}, "
-                            f"rr_depth={args.rr_depth}",
-                "global_spp": spp,
-                "spp_per_rank": s1 - s0,
-                "paths_per_step": W * H * spp,
-                "parallelism": f"sample-range shards x{world}" + (", RCCL slice-reduce of films to rank 0" if world > 1 else ""),
-            },
+            **head,
             "roofline": {
                 # the busier of the two units the traversal can saturate, from the
                 # build's unit counters (TA 0.75 vs VALU 0.54 in profiles/r3d_pmc_units.json)

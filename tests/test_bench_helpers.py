@@ -42,6 +42,46 @@ def test_units_and_traffic_match_build_and_args(tmp_path, monkeypatch):
     assert got[k] == 5
 
 
+def test_full_is_off_by_default_and_gates_the_counter_step_film(monkeypatch):
+    import pytest
+
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs == "" and args.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d", "--dump-film", "f.npy"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "d"
+    for bad in (["--dump-film", "f.npy"], ["--steps", "0"], ["--workload", "prims", "--dump-outputs", "d"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
+        with pytest.raises(SystemExit):
+            bench.parse()
+
+
+def test_dump_outputs_writes_the_film_or_a_fixed_row_sample(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    import bench
+
+    film = torch.arange(6 * 5 * 4, dtype=torch.float32).reshape(6, 5, 4)
+    bench.dump_outputs(film, str(tmp_path / "a"))
+    got = np.load(tmp_path / "a" / "film.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, film.numpy())
+    assert not (tmp_path / "a" / "film_rows.npy").exists()
+    # above the size limit: the same seeded rows on every run, within the limit
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 * film[0].numel() * 4 + 8 * 6)
+    for d in ("b", "c"):
+        bench.dump_outputs(film, str(tmp_path / d))
+    rows = np.load(tmp_path / "b" / "film_rows.npy")
+    got = np.load(tmp_path / "b" / "film.npy")
+    assert rows.dtype == np.float64 and len(rows) == 3 and len(set(rows)) == 3
+    assert np.array_equal(got, film.numpy()[rows.astype(int)])
+    assert got.nbytes + rows.nbytes <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "film_rows.npy"))
+
+
 def test_vmem_peak_from_probe():
     """The roofline peak is the probe's byte rate of the vector-memory path
     (1 KiB per 16.9 CU-cycles, profiles/r3_ta_rate.txt) x 256 CUs x 2.4 GHz."""

@@ -210,7 +210,7 @@ def _bench_film(tmp_path, n, backend="gloo"):
     out = os.path.join(tmp_path, f"film{n}.npy")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--backend", backend,
            "--width", "64", "--height", "36", "--spp", "8", "--steps", "1", "--warmup", "0",
-           "--no-cpu-baseline", "--dump-film", out, "--master-port", str(_free_port())]
+           "--full", "--no-cpu-baseline", "--dump-film", out, "--master-port", str(_free_port())]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
@@ -230,3 +230,38 @@ def test_bench_gpus2_strong_scaling(tmp_path):
     assert l2["config"]["spp_per_rank"] == 4 and l2["scaling"] == "strong"
     assert l1["roofline"]["frac"] <= 1.0
     np.testing.assert_array_equal(f2, f1)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_headline_and_dumped_film(tmp_path, full_scene):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` prints the headline
+    fields only (roofline, per-kernel figures and the CPU baseline are behind
+    --full) and `--dump-outputs DIR` writes the film of the last timed step:
+    step K-1 renders seed K-1, so DIR/film.npy is render_film(seed=K-1)."""
+    import json
+    import subprocess
+    import sys
+
+    from mtx import PathIntegrator
+
+    d = os.path.join(tmp_path, "out")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--width", "64", "--height", "36", "--spp", "8", "--dump-outputs", d]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "Mpaths/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["ms_per_step"] > 0
+    # value is the paths of the timed steps over their time
+    assert abs(line["value"] - 64 * 36 * 8 / (line["ms_per_step"] * 1e3)) <= 0.01 * line["value"] + 1e-3
+    for k in ("roofline", "kernels", "cpu_baseline"):
+        assert k not in line
+    assert os.listdir(d) == ["film.npy"]
+    film = np.load(os.path.join(d, "film.npy"))
+    assert film.dtype == np.float32 and film.shape == (38, 66, 4)
+    integ = PathIntegrator({"max_depth": 8, "rr_depth": 2})
+    ref = integ.render_film(full_scene.with_film(64, 36), seed=1, spp=8)
+    np.testing.assert_array_equal(film, ref)

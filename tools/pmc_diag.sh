@@ -6,7 +6,7 @@
 set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/diag_${1:-a}
-BARGS=${2:-"--steps 1 --warmup 0 --no-cpu-baseline"}
+BARGS=${2:-"--steps 1 --warmup 0 --full --no-cpu-baseline"}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 120 rocprofv3 -L > $OUT/counters.txt 2>&1 || { echo "rocprofv3 -L failed"; tail -3 $OUT/counters.txt; exit 1; }

@@ -8,14 +8,14 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out
 TAG=${1:-r2}
-BARGS="--steps 1 --warmup 0 --no-cpu-baseline"
+BARGS="--steps 1 --warmup 0 --full --no-cpu-baseline"
 mkdir -p $OUT
 cd $R
-echo "== bench"; timeout -k 10 400 python3 bench.py --steps 5 --warmup 2 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+echo "== bench"; timeout -k 10 400 python3 bench.py --full --steps 5 --warmup 2 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 rc=$?; cut -c1-300 $OUT/bench_$TAG.json; [ $rc -ne 0 ] && { tail -5 $OUT/bench_$TAG.err; exit $rc; }
 cd /tmp && export TMPDIR=/tmp
 echo "== kernel trace"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o trace --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/prof_${TAG}_trace.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o trace --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > $OUT/prof_${TAG}_trace.log 2>&1
 rc=$?; [ $rc -ne 0 ] && { echo "trace rc=$rc"; tail -5 $OUT/prof_${TAG}_trace.log; exit $rc; }
 tail -1 $OUT/prof_${TAG}_trace.log | cut -c1-200
 for c in FETCH_SIZE WRITE_SIZE; do

@@ -21,7 +21,7 @@ else
   bash tools/profile_workloads.sh $TAG restir nrc pssmlt || exit 1
   cp $OUT/${TAG}_*_pmc_traffic.json $OUT/${TAG}_*_pmc_units.json profiles/ || exit 1
   echo "== bench"
-  timeout -k 10 400 python3 bench.py --steps 5 --warmup 2 > $OUT/bench2_$TAG.json 2> $OUT/bench2_$TAG.err || { tail -5 $OUT/bench2_$TAG.err; exit 1; }
+  timeout -k 10 400 python3 bench.py --full --steps 5 --warmup 2 > $OUT/bench2_$TAG.json 2> $OUT/bench2_$TAG.err || { tail -5 $OUT/bench2_$TAG.err; exit 1; }
   cut -c1-300 $OUT/bench2_$TAG.json
   bash tools/workload_session.sh $TAG nrc restir prims pssmlt
 fi
