@@ -241,8 +241,18 @@ typedef struct mtx_render_args {
   uint32_t max_M_spatial;  /* 0 = None */
   float initial_search_radius;
   float minimal_search_radius;
-  uint32_t reserved;
+  uint32_t rfilter;      /* MTX_RFILTER_*: the film's reconstruction filter (mtx_render only; 0 = tent,
+                            so callers that zeroed the former `reserved` word are unchanged) */
 } mtx_render_args;
+
+/* Reconstruction filters of the film (mtx_core/film.h; Mitsuba's `tent`,
+ * `box` and `gaussian` rfilter plugins). border = the filter's reach in
+ * pixels = the border of the raw film on every side. */
+#ifndef MTX_RFILTER_TENT
+#define MTX_RFILTER_TENT 0u     /* radius 1,   border 1: max(0, 1 - |r|) */
+#define MTX_RFILTER_BOX 1u      /* radius 0.5, border 0: the sample goes to its own pixel with weight 1 */
+#define MTX_RFILTER_GAUSSIAN 2u /* radius 2,   border 2: stddev 0.5, max(0, exp(-2 r^2) - exp(-8)) */
+#endif
 
 enum {
   MTX_RESTIR_BIAS_CORRECTION = 1,
@@ -314,10 +324,14 @@ int mtx_roughplastic_tables(uint32_t distribution, float alpha, float eta, float
 int mtx_scene_upload(mtx_ctx *ctx, const mtx_scene_desc *scene);
 
 /* --------------------------- integrators -------------------------- */
-/* Render film rows [y0,y1) (+1-pixel tent border) into film_rgbw, an
- * (y1-y0+2) x (width+2) x 4 float buffer (host pointer, or a device pointer
- * when film_on_device != 0): un-normalised RGB*weight and weight sums in a
- * fixed summation order. Replaces mi.render(scene, integrator, spp, seed)
+/* Render film rows [y0,y1) plus the border b of args->rfilter into
+ * film_rgbw, an (y1-y0+2b) x (width+2b) x 4 float buffer (host pointer, or a
+ * device pointer when film_on_device != 0): un-normalised RGB*weight and
+ * weight sums in a fixed summation order. Film shape per filter:
+ *   MTX_RFILTER_TENT (0, the default)  b = 1  (y1-y0+2) x (width+2) x 4
+ *   MTX_RFILTER_BOX                    b = 0  (y1-y0)   x  width    x 4
+ *   MTX_RFILTER_GAUSSIAN               b = 2  (y1-y0+4) x (width+4) x 4
+ * An unknown filter id is MTX_E_ARG and nothing is rendered. Replaces mi.render(scene, integrator, spp, seed)
  * driving SamplingIntegrator::render (transcribed path.py:103-192) with the
  * sample() of path.py:194-302 / path-mis.py:24-155 / nrc.py:104-125,
  * Pssmlt.render (pssmlt.py:167-228), and one RestirIntegrator.render frame
@@ -383,6 +397,15 @@ int mtx_trace(mtx_ctx *ctx, uint64_t n, const float *rays, int any_hit, uint32_t
 /* mtx_trace on device buffers (Scene.ray_intersect on a device wavefront). */
 int mtx_trace_dev(mtx_ctx *ctx, uint64_t n, const float *rays, int any_hit, uint32_t *hits,
                   uint32_t *visits);
+
+/* --------------------------- film filters ------------------------- */
+/* Host-only: border (pixels on every side of the raw film) and radius of a
+ * reconstruction filter; either output may be NULL. Unknown id: MTX_E_ARG. */
+int mtx_rfilter_info(uint32_t rfilter, uint32_t *border_out, float *radius_out);
+/* Host-only: the filter's one-axis weight (the function the film kernels
+ * evaluate, mtx_core/film.h rfilter_eval) at n offsets r from a pixel centre;
+ * a sample's weight is the product over x and y. Box: 1 for |r| <= 0.5, else 0. */
+int mtx_rfilter_eval(uint32_t rfilter, const float *r, float *w_out, uint64_t n);
 
 /* --------------------------- primitives --------------------------- */
 /* prefix_sum.py:9-36: inclusive (or exclusive) scan of u32, device-wide

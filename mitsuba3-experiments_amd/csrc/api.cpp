@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "mtx.h"
+#include "mtx_core/film.h"
 #include "mtx_core/interaction.h"
 #include "prims.h"
 #include "wavefront.h"
@@ -1167,6 +1168,7 @@ int render_restir(mtx_ctx *c, const mtx_render_args *a, float4 *film_dev, Timer 
   p.n_px = (a->y1 - a->y0) * W;
   p.band_y0 = a->y0;
   p.band_px = (a->y1 - a->y0) * W;
+  p.rfilter = a->rfilter;
   p.n_paths = nb;
   p.restir = 1;
   p.stats = want_stats ? 1 : 0;
@@ -1296,7 +1298,7 @@ int render_restir(mtx_ctx *c, const mtx_render_args *a, float4 *film_dev, Timer 
     }
     mtxd::launch_restir_final(c->scene, b, p, r, st);
     mtxd::launch_film_src(b, p, (float4 *)c->contrib.p, st);
-    mtxd::launch_film_gather((const float4 *)c->contrib.p, film_dev, W, a->y0, a->y1, 1, 1u, st);
+    mtxd::launch_film_gather((const float4 *)c->contrib.p, film_dev, W, a->y0, a->y1, 1, 1u, a->rfilter, st);
   }
   HIP_TRY(hipGetLastError());
   if (only_a) {
@@ -1326,6 +1328,14 @@ int mtx_render(mtx_ctx *c, const mtx_render_args *a, float *film_rgbw, int film_
     mtx_set_error("mtx_render: bad film/rows/spp arguments");
     return MTX_E_ARG;
   }
+  if (a->rfilter >= mtx::kRfilterCount) {
+    mtx_set_error("mtx_render: unknown reconstruction filter %u (MTX_RFILTER_TENT 0, _BOX 1, _GAUSSIAN 2)",
+                  a->rfilter);
+    return MTX_E_ARG;
+  }
+  // the film's border and the taps per source pixel follow the filter (mtx_core/film.h)
+  const uint32_t fb = mtx::rfilter_reach(a->rfilter);
+  const uint64_t taps = (uint64_t)(2 * fb + 1) * (2 * fb + 1);
   if ((uint64_t)W * H * a->spp_total >= (1ull << 32)) {
     mtx_set_error("mtx_render: W*H*spp_total exceeds the 32-bit sampler lane space");
     return MTX_E_ARG;
@@ -1375,8 +1385,8 @@ int mtx_render(mtx_ctx *c, const mtx_render_args *a, float *film_rgbw, int film_
         slot_mask |= 1u << k;
     }
   }
-  if ((rc = dalloc(c->contrib, 9ull * 16 * band_px * film_slots))) return rc;
-  const size_t film_floats = 4ull * (W + 2) * (a->y1 - a->y0 + 2);
+  if ((rc = dalloc(c->contrib, taps * 16 * band_px * film_slots))) return rc;
+  const size_t film_floats = 4ull * (W + 2 * fb) * (a->y1 - a->y0 + 2 * fb);
   float4 *film_dev = (float4 *)film_rgbw;
   if (!film_on_device) {
     if ((rc = dalloc(c->film, film_floats * 4))) return rc;
@@ -1401,7 +1411,7 @@ int mtx_render(mtx_ctx *c, const mtx_render_args *a, float *film_rgbw, int film_
   if (mlt) {
     if ((rc = ensure_mlt(c, cap, std::max<uint32_t>(a->max_depth, 1), a->integrator == MTX_INT_PSSMLT_PATH)))
       return rc;
-    HIP_TRY(hipMemsetAsync(c->contrib.p, 0, 9ull * 16 * band_px, c->stream));
+    HIP_TRY(hipMemsetAsync(c->contrib.p, 0, taps * 16 * band_px, c->stream));
   }
   mtxd::WaveBuffers b = buffers(c);
   if (want_stats) HIP_TRY(hipMemsetAsync(b.stats, 0, 64, c->stream));
@@ -1438,6 +1448,7 @@ int mtx_render(mtx_ctx *c, const mtx_render_args *a, float *film_rgbw, int film_
     p.band_y0 = a->y0;
     p.band_px = (a->y1 - a->y0) * W;
     p.film_slots = film_slots;
+    p.rfilter = a->rfilter;
     p.slot_mask = slot_mask;
     p.n_paths = p.n_px * a->spp;
     p.nrc_c = a->nrc_c;
@@ -1481,13 +1492,37 @@ int mtx_render(mtx_ctx *c, const mtx_render_args *a, float *film_rgbw, int film_
     HIP_TRY(hipEventRecord(c->w2.done, c->w2.stream));
     HIP_TRY(hipStreamWaitEvent(c->stream, c->w2.done, 0));
   }
-  mtxd::launch_film_gather((const float4 *)c->contrib.p, film_dev, W, a->y0, a->y1, film_slots, slot_mask, c->stream);
+  mtxd::launch_film_gather((const float4 *)c->contrib.p, film_dev, W, a->y0, a->y1, film_slots, slot_mask, a->rfilter,
+                           c->stream);
   tm.end(3, e_all);
   HIP_TRY(hipGetLastError());
   if (!film_on_device)
     HIP_TRY(hipMemcpyAsync(film_rgbw, film_dev, film_floats * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return fill_stats(c, stats, want_stats, tm, n_trace, n_shadow, (uint64_t)band_px * a->spp);
+}
+
+int mtx_rfilter_info(uint32_t rfilter, uint32_t *border_out, float *radius_out) {
+  if (rfilter >= mtx::kRfilterCount) {
+    mtx_set_error("mtx_rfilter_info: unknown reconstruction filter %u", rfilter);
+    return MTX_E_ARG;
+  }
+  if (border_out) *border_out = mtx::rfilter_reach(rfilter);
+  if (radius_out) *radius_out = mtx::rfilter_radius(rfilter);
+  return MTX_OK;
+}
+
+int mtx_rfilter_eval(uint32_t rfilter, const float *r, float *w_out, uint64_t n) {
+  if (rfilter >= mtx::kRfilterCount) {
+    mtx_set_error("mtx_rfilter_eval: unknown reconstruction filter %u", rfilter);
+    return MTX_E_ARG;
+  }
+  if (n && (!r || !w_out)) {
+    mtx_set_error("mtx_rfilter_eval: null argument");
+    return MTX_E_ARG;
+  }
+  for (uint64_t i = 0; i < n; ++i) w_out[i] = mtx::rfilter_eval(rfilter, r[i]);
+  return MTX_OK;
 }
 
 int mtx_set_camera(mtx_ctx *c, const mtx_camera *cam) {

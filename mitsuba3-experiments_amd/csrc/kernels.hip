@@ -15,7 +15,8 @@
 //   shadow   persistent any-hit traversal of the NEE rays; visible ones add
 //            their contribution to L (Scene.ray_test inside
 //            sample_emitter_direction(..., test_visibility=True), path.py:247)
-//   film     deterministic gather-form tent splat (ImageBlock.put, path.py:101)
+//   film     deterministic gather-form splat with the tent (default), box or
+//            gaussian reconstruction filter (ImageBlock.put, path.py:101)
 //
 // All arithmetic is IEEE fp32 with -ffp-contract=off; the per-lane
 // primitives are the shared mtx_core headers, so every lane reproduces the
@@ -25,6 +26,7 @@
 #include <algorithm>
 
 #include "device_common.h"
+#include "mtx_core/film.h"
 #include "restir_dev.h"
 
 using namespace mtx;
@@ -1393,8 +1395,11 @@ __global__ void k_cache_apply(WaveBuffers b, const float *out, const uint32_t *p
 }
 
 // ---------------------------------------------------------------------------
-// Film: stage 1 per source pixel (3x3 tent footprint, samples in order),
-// stage 2 per film pixel (9 neighbours in fixed order). See DESIGN.md.
+// Film: stage 1 per source pixel ((2N+1)^2 footprint of the reconstruction
+// filter, samples in order), stage 2 per film pixel (the (2N+1)^2 neighbours
+// in fixed order). The kernels are templates on the filter's reach N and the
+// filter F (mtx_core/film.h): <1, tent> is the default, <0, box> and
+// <2, gaussian> are opt-in (mtx_render_args.rfilter). See DESIGN.md.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ V3 final_L(const WaveBuffers &b, const ChunkParams &p, uint32_t path) {
   const float4 l = b.L[kFinal][path];
@@ -1408,15 +1413,25 @@ __device__ __forceinline__ V3 final_L(const WaveBuffers &b, const ChunkParams &p
 // lane accumulates its own pixel in sample order (same order as below).
 constexpr int kFilmStage = 8;  // 8 (11.5 KB of LDS per wave, twice the waves per CU) beat 16 by 0.8 ms, and 4
 
-__device__ __forceinline__ void film_accumulate(float4 acc[9], int x, int y, float2 ps, V3 L) {
+constexpr int film_taps(int N) { return (2 * N + 1) * (2 * N + 1); }
+// Block-size bound of the per-pixel kernels launched with 128 threads: the
+// gaussian's 25 float4 accumulators need more than the 128 VGPRs the default
+// bound (1024 threads) leaves a lane; the tent and the box keep the default.
+constexpr int film_max_block(int N) { return N == 2 ? 128 : 1024; }
+
+template <int N, uint32_t F>
+__device__ __forceinline__ void film_accumulate(float4 *acc, int x, int y, float2 ps, V3 L) {
+  constexpr int D = 2 * N + 1;
+  float wxs[D];
 #pragma unroll
-  for (int dy = 0; dy < 3; ++dy) {
-    const float wy = fmaxf(0.f, 1.f - fabsf(ps.y - ((float)(y + dy - 1) + 0.5f)));
+  for (int dx = 0; dx < D; ++dx) wxs[dx] = rfilter_eval(F, ps.x - ((float)(x + dx - N) + 0.5f));
 #pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {
-      const float wx = fmaxf(0.f, 1.f - fabsf(ps.x - ((float)(x + dx - 1) + 0.5f)));
-      const float w = wx * wy;
-      float4 &c = acc[dy * 3 + dx];
+  for (int dy = 0; dy < D; ++dy) {
+    const float wy = rfilter_eval(F, ps.y - ((float)(y + dy - N) + 0.5f));
+#pragma unroll
+    for (int dx = 0; dx < D; ++dx) {
+      const float w = wxs[dx] * wy;
+      float4 &c = acc[dy * D + dx];
       c.x = c.x + L.x * w;
       c.y = c.y + L.y * w;
       c.z = c.z + L.z * w;
@@ -1429,7 +1444,8 @@ __device__ __forceinline__ void film_accumulate(float4 acc[9], int x, int y, flo
 // a lane moves on to the next slot's contribution planes whenever its sample
 // index passes a slot end (the same for every lane of the launch: no
 // divergence) and writes all 8 slots (zeros for slots without samples);
-// otherwise one slot. contrib: [slot][9][band_px].
+// otherwise one slot. contrib: [slot][K][band_px], K = (2N+1)^2 taps.
+template <int K>
 struct FilmSlots {
   uint32_t cur, end, T, mask;
   bool eight;
@@ -1440,18 +1456,18 @@ struct FilmSlots {
     cur = 0;
     end = eight ? film_slot_end(0, T) : 0xffffffffu;
   }
-  __device__ __forceinline__ void flush(float4 acc[9], float4 *contrib, const ChunkParams &p, size_t o) {
+  __device__ __forceinline__ void flush(float4 *acc, float4 *contrib, const ChunkParams &p, size_t o) {
     const bool used = (mask >> cur) & 1u;  // a slot without samples of this render stays unwritten
 #pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      if (used) contrib[((size_t)cur * 9 + k) * p.band_px + o] = acc[k];
+    for (int k = 0; k < K; ++k) {
+      if (used) contrib[((size_t)cur * K + k) * p.band_px + o] = acc[k];
       acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     ++cur;
     end = cur < 7 ? film_slot_end(cur, T) : 0xffffffffu;
   }
   // before accumulating global sample g
-  __device__ __forceinline__ void advance(uint32_t g, float4 acc[9], float4 *contrib, const ChunkParams &p, size_t o,
+  __device__ __forceinline__ void advance(uint32_t g, float4 *acc, float4 *contrib, const ChunkParams &p, size_t o,
                                           bool write) {
     while (g >= end) {
       if (write) {
@@ -1462,26 +1478,27 @@ struct FilmSlots {
       }
     }
   }
-  __device__ __forceinline__ void finish(float4 acc[9], float4 *contrib, const ChunkParams &p, size_t o) {
+  __device__ __forceinline__ void finish(float4 *acc, float4 *contrib, const ChunkParams &p, size_t o) {
     const uint32_t n = eight ? 8u : 1u;
     while (cur < n) flush(acc, contrib, p, o);
   }
 };
 
+template <int N, uint32_t F>
 __global__ __launch_bounds__(64) void k_film_src_staged(WaveBuffers b, ChunkParams p, float4 *contrib) {
-  constexpr int S = kFilmStage;
+  constexpr int S = kFilmStage, K = film_taps(N);
   __shared__ float sv[5][64][S + 1];  // L.xyz, pos.xy
   const uint32_t q0 = blockIdx.x * 64, lane = threadIdx.x, q = q0 + lane;
   const uint32_t pix = p.px0 + q;
   const int y = (int)(pix / p.width), x = (int)(pix - (uint32_t)y * p.width);
   const bool mask_valid = p.integrator == MTX_INT_PATH_MIS;
   const bool live = q < p.n_px;
-  const size_t o = (size_t)(pix - p.band_y0 * p.width);  // contrib: [slot][9][band_px]
-  FilmSlots fs;
+  const size_t o = (size_t)(pix - p.band_y0 * p.width);  // contrib: [slot][K][band_px]
+  FilmSlots<K> fs;
   fs.init(p);
-  float4 acc[9];
+  float4 acc[K];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int k = 0; k < K; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
   for (uint32_t s0 = 0; s0 < p.spp; s0 += S) {
     const uint32_t ns = min((uint32_t)S, p.spp - s0);
 #pragma unroll 4
@@ -1503,8 +1520,8 @@ __global__ __launch_bounds__(64) void k_film_src_staged(WaveBuffers b, ChunkPara
     for (uint32_t sm = 0; sm < ns; ++sm) {
       fs.advance(p.sample_offset + s0 + sm, acc, contrib, p, o, live);
       if (live)
-        film_accumulate(acc, x, y, make_float2(sv[3][lane][sm], sv[4][lane][sm]),
-                        V3{sv[0][lane][sm], sv[1][lane][sm], sv[2][lane][sm]});
+        film_accumulate<N, F>(acc, x, y, make_float2(sv[3][lane][sm], sv[4][lane][sm]),
+                              V3{sv[0][lane][sm], sv[1][lane][sm], sv[2][lane][sm]});
     }
     __syncthreads();
   }
@@ -1512,36 +1529,40 @@ __global__ __launch_bounds__(64) void k_film_src_staged(WaveBuffers b, ChunkPara
   fs.finish(acc, contrib, p, o);
 }
 
-__global__ void k_film_src(WaveBuffers b, ChunkParams p, float4 *contrib) {
+template <int N, uint32_t F>
+__global__ __launch_bounds__(film_max_block(N)) void k_film_src(WaveBuffers b, ChunkParams p, float4 *contrib) {
+  constexpr int K = film_taps(N);
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= p.n_px) return;
   const uint32_t pix = p.px0 + q;
   const int y = (int)(pix / p.width), x = (int)(pix - (uint32_t)y * p.width);
-  const size_t o = (size_t)(pix - p.band_y0 * p.width);  // contrib: [slot][9][band_px]
-  FilmSlots fs;
+  const size_t o = (size_t)(pix - p.band_y0 * p.width);  // contrib: [slot][K][band_px]
+  FilmSlots<K> fs;
   fs.init(p);
-  float4 acc[9];
+  float4 acc[K];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int k = 0; k < K; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
   for (uint32_t sidx = 0; sidx < p.spp; ++sidx) {
     fs.advance(p.sample_offset + sidx, acc, contrib, p, o, true);
     const uint32_t path = q * p.spp + sidx;
-    film_accumulate(acc, x, y, b.pos[path], final_L(b, p, path));
+    film_accumulate<N, F>(acc, x, y, b.pos[path], final_L(b, p, path));
   }
   fs.finish(acc, contrib, p, o);
 }
 
-// Stage 2: per film pixel and slot the 9 neighbours in (dy, dx) order, then
+// Stage 2: per film pixel and slot the (2N+1)^2 neighbours in (dy, dx) order, then
 // the slots' fixed binary tree (film_tree8) when nslots == 8. Slots outside
 // slot_mask hold no sample of the render: they are zero, not read (a sum
 // that starts at +0 never becomes -0, so adding their +0 changes nothing).
+template <int N>
 __global__ void k_film_gather(const float4 *contrib, float4 *film, uint32_t W, uint32_t y0, uint32_t y1,
                               uint32_t nslots, uint32_t slot_mask) {
-  const uint32_t FW = W + 2, FH = (y1 - y0) + 2;
-  const size_t P = (size_t)(y1 - y0) * W;  // contrib: [slot][9][band pixels]
+  constexpr int D = 2 * N + 1, K = D * D;
+  const uint32_t FW = W + 2 * N, FH = (y1 - y0) + 2 * N;
+  const size_t P = (size_t)(y1 - y0) * W;  // contrib: [slot][K][band pixels]
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= FW * FH) return;
-  const int px = (int)(q % FW) - 1, py = (int)(y0 + q / FW) - 1;
+  const int px = (int)(q % FW) - N, py = (int)(y0 + q / FW) - N;
   V4 sl[8];
   const uint32_t ns = nslots == 8 ? 8u : 1u;
   for (uint32_t k = 0; k < ns; ++k) {
@@ -1551,12 +1572,12 @@ __global__ void k_film_gather(const float4 *contrib, float4 *film, uint32_t W, u
       continue;
     }
 #pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
+    for (int dy = 0; dy < D; ++dy)
 #pragma unroll
-      for (int dx = 0; dx < 3; ++dx) {
-        const int sxp = px - dx + 1, syp = py - dy + 1;
+      for (int dx = 0; dx < D; ++dx) {
+        const int sxp = px - dx + N, syp = py - dy + N;
         if (sxp < 0 || sxp >= (int)W || syp < (int)y0 || syp >= (int)y1) continue;
-        const float4 c = contrib[((size_t)k * 9 + (size_t)(dy * 3 + dx)) * P + (size_t)(syp - (int)y0) * W + sxp];
+        const float4 c = contrib[((size_t)k * K + (size_t)(dy * D + dx)) * P + (size_t)(syp - (int)y0) * W + sxp];
         r = r + c.x;
         g = g + c.y;
         bl = bl + c.z;
@@ -1722,37 +1743,26 @@ __global__ void k_mlt_end(WaveBuffers b, ChunkParams p, uint32_t max_depth) {
 
 // block.put(pos, L / cw) at the integer pixel position (:161-165), running
 // accumulation per source pixel: iteration, then chain order.
-__global__ void k_mlt_film(WaveBuffers b, ChunkParams p, float4 *contrib) {
+template <int N, uint32_t F>
+__global__ __launch_bounds__(film_max_block(N)) void k_mlt_film(WaveBuffers b, ChunkParams p, float4 *contrib) {
+  constexpr int K = film_taps(N);
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= p.n_px) return;
   const uint32_t pix = p.px0 + q;
   const int y = (int)(pix / p.width), x = (int)(pix - (uint32_t)y * p.width);
-  const size_t o = (size_t)(pix - p.band_y0 * p.width);  // contrib: 9 planes of band_px
-  float4 acc[9];
+  const size_t o = (size_t)(pix - p.band_y0 * p.width);  // contrib: K planes of band_px
+  float4 acc[K];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) acc[k] = contrib[(size_t)k * p.band_px + o];
+  for (int k = 0; k < K; ++k) acc[k] = contrib[(size_t)k * p.band_px + o];
   for (uint32_t sidx = 0; sidx < p.spp; ++sidx) {
     const uint32_t c = q * p.spp + sidx;
     const float4 lc = b.mlt_L[c];
     const float cw = b.mlt_cur[c].z;
     const V3 res = V3{lc.x, lc.y, lc.z} / cw;
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy) {
-      const float wy = fmaxf(0.f, 1.f - fabsf((float)y - ((float)(y + dy - 1) + 0.5f)));
-#pragma unroll
-      for (int dx = 0; dx < 3; ++dx) {
-        const float wx = fmaxf(0.f, 1.f - fabsf((float)x - ((float)(x + dx - 1) + 0.5f)));
-        const float w = wx * wy;
-        float4 &a = acc[dy * 3 + dx];
-        a.x = a.x + res.x * w;
-        a.y = a.y + res.y * w;
-        a.z = a.z + res.z * w;
-        a.w = a.w + w;
-      }
-    }
+    film_accumulate<N, F>(acc, x, y, make_float2((float)x, (float)y), res);
   }
 #pragma unroll
-  for (int k = 0; k < 9; ++k) contrib[(size_t)k * p.band_px + o] = acc[k];
+  for (int k = 0; k < K; ++k) contrib[(size_t)k * p.band_px + o] = acc[k];
 }
 
 // ---------------------------------------------------------------------------
@@ -1886,20 +1896,45 @@ void launch_mlt_begin(const DevScene &s, const WaveBuffers &b, const ChunkParams
 void launch_mlt_end(const WaveBuffers &b, const ChunkParams &p, hipStream_t st) {
   hipLaunchKernelGGL(k_mlt_end, dim3(blocks_for(p.n_paths, 256)), dim3(256), 0, st, b, p, p.max_depth);
 }
+// p.rfilter picks the instantiation; mtx_render has refused unknown ids.
+template <int N, uint32_t F>
+static void launch_mlt_film_t(const WaveBuffers &b, const ChunkParams &p, float4 *contrib, hipStream_t st) {
+  hipLaunchKernelGGL((k_mlt_film<N, F>), dim3(blocks_for(p.n_px, 128)), dim3(128), 0, st, b, p, contrib);
+}
 void launch_mlt_film(const WaveBuffers &b, const ChunkParams &p, float4 *contrib, hipStream_t st) {
-  hipLaunchKernelGGL(k_mlt_film, dim3(blocks_for(p.n_px, 128)), dim3(128), 0, st, b, p, contrib);
+  if (p.rfilter == MTX_RFILTER_BOX)
+    launch_mlt_film_t<0, MTX_RFILTER_BOX>(b, p, contrib, st);
+  else if (p.rfilter == MTX_RFILTER_GAUSSIAN)
+    launch_mlt_film_t<2, MTX_RFILTER_GAUSSIAN>(b, p, contrib, st);
+  else
+    launch_mlt_film_t<1, MTX_RFILTER_TENT>(b, p, contrib, st);
+}
+template <int N, uint32_t F>
+static void launch_film_src_t(const WaveBuffers &b, const ChunkParams &p, float4 *contrib, hipStream_t st) {
+  if (p.spp < 4)
+    hipLaunchKernelGGL((k_film_src<N, F>), dim3(blocks_for(p.n_px, 128)), dim3(128), 0, st, b, p, contrib);
+  else
+    hipLaunchKernelGGL((k_film_src_staged<N, F>), dim3(blocks_for(p.n_px, 64)), dim3(64), 0, st, b, p, contrib);
 }
 void launch_film_src(const WaveBuffers &b, const ChunkParams &p, float4 *contrib, hipStream_t st) {
-  if (p.spp < 4)
-    hipLaunchKernelGGL(k_film_src, dim3(blocks_for(p.n_px, 128)), dim3(128), 0, st, b, p, contrib);
+  if (p.rfilter == MTX_RFILTER_BOX)
+    launch_film_src_t<0, MTX_RFILTER_BOX>(b, p, contrib, st);
+  else if (p.rfilter == MTX_RFILTER_GAUSSIAN)
+    launch_film_src_t<2, MTX_RFILTER_GAUSSIAN>(b, p, contrib, st);
   else
-    hipLaunchKernelGGL(k_film_src_staged, dim3(blocks_for(p.n_px, 64)), dim3(64), 0, st, b, p, contrib);
+    launch_film_src_t<1, MTX_RFILTER_TENT>(b, p, contrib, st);
 }
 void launch_film_gather(const float4 *contrib, float4 *film, uint32_t width, uint32_t y0, uint32_t y1,
-                        uint32_t nslots, uint32_t slot_mask, hipStream_t st) {
-  const uint64_t n = (uint64_t)(width + 2) * (y1 - y0 + 2);
-  hipLaunchKernelGGL(k_film_gather, dim3(blocks_for(n, 256)), dim3(256), 0, st, contrib, film, width, y0, y1, nslots,
-                     slot_mask);
+                        uint32_t nslots, uint32_t slot_mask, uint32_t rfilter, hipStream_t st) {
+  const uint32_t nb = rfilter_reach(rfilter);
+  const uint64_t n = (uint64_t)(width + 2 * nb) * (y1 - y0 + 2 * nb);
+  const dim3 grid(blocks_for(n, 256)), block(256);
+  if (rfilter == MTX_RFILTER_BOX)
+    hipLaunchKernelGGL(k_film_gather<0>, grid, block, 0, st, contrib, film, width, y0, y1, nslots, slot_mask);
+  else if (rfilter == MTX_RFILTER_GAUSSIAN)
+    hipLaunchKernelGGL(k_film_gather<2>, grid, block, 0, st, contrib, film, width, y0, y1, nslots, slot_mask);
+  else
+    hipLaunchKernelGGL(k_film_gather<1>, grid, block, 0, st, contrib, film, width, y0, y1, nslots, slot_mask);
 }
 void launch_collect(const WaveBuffers &b, const ChunkParams &p, float *L_out, uint8_t *valid_out, hipStream_t st) {
   hipLaunchKernelGGL(k_collect, dim3(blocks_for(p.n_paths, 256)), dim3(256), 0, st, b, p, L_out, valid_out);

@@ -22,6 +22,7 @@ from .integrators import (  # noqa: F401
     mtx_scene_of,
     register_integrator,
     register_with_mitsuba,
+    rfilter_border,
     scene_with_sensor,
     trace_rays,
 )

@@ -37,6 +37,12 @@ MTX_RENDER_TIMING = 2
 MTX_RENDER_NRC_CACHE = 4
 MTX_RESTIR_STAGE_B = 32
 
+MTX_RFILTER_TENT = 0       # film reconstruction filters (mtx_core/film.h)
+MTX_RFILTER_BOX = 1
+MTX_RFILTER_GAUSSIAN = 2
+RFILTERS = {"tent": MTX_RFILTER_TENT, "box": MTX_RFILTER_BOX, "gaussian": MTX_RFILTER_GAUSSIAN}
+RFILTER_BORDER = {MTX_RFILTER_TENT: 1, MTX_RFILTER_BOX: 0, MTX_RFILTER_GAUSSIAN: 2}
+
 MTX_ROUGH_TRANSMITTANCE_RES = 64
 MTX_BVH_WIDTH = 4          # closest-hit BVH (mtx.h)
 MTX_BVH_MAX_LEAF = 8
@@ -160,7 +166,7 @@ class RenderArgs(C.Structure):
         ("max_M_spatial", C.c_uint32),
         ("initial_search_radius", C.c_float),
         ("minimal_search_radius", C.c_float),
-        ("reserved", C.c_uint32),
+        ("rfilter", C.c_uint32),
     ]
 
 
@@ -307,4 +313,6 @@ EXPORTS = [
     "mtx_nerad_lhs",
     "mtx_nerad_rhs",
     "mtx_nerad_step",
+    "mtx_rfilter_info",
+    "mtx_rfilter_eval",
 ]

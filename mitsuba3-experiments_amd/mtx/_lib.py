@@ -87,6 +87,8 @@ def lib() -> C.CDLL:
         "mtx_nerad_lhs": ([vp, C.POINTER(_abi.NeradArgs), vp], C.c_int),
         "mtx_nerad_rhs": ([vp, C.POINTER(_abi.NeradArgs), vp, vp], C.c_int),
         "mtx_nerad_step": ([vp, C.POINTER(_abi.NeradArgs), C.POINTER(_abi.TrainStats)], C.c_int),
+        "mtx_rfilter_info": ([u32, C.POINTER(u32), C.POINTER(C.c_float)], C.c_int),
+        "mtx_rfilter_eval": ([u32, vp, vp, u64], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

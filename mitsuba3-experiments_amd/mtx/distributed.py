@@ -8,8 +8,9 @@ naturally (§8e):
     (deterministic; at N = 2, 4, 8 the top of the film's 8-slot tree, so the
     combined film equals the one-GPU film bit for bit).
   * row bands (strong scaling): rank r traces film rows [y0_r, y1_r); each
-    band carries its 1-row tent halo above and below, stitched on rank 0 by
-    adding the overlapping halo rows in rank order.
+    band carries the border of its reconstruction filter above and below (1
+    row for the tent, 2 for the gaussian, none for the box), stitched on rank
+    0 by adding the overlapping border rows in rank order.
 One collective per render (a gather of ~15 MB films to rank 0 for 1280x720);
 no data-path exchange during tracing.
 
@@ -146,15 +147,37 @@ def reduce_sum(film, group=None):
     return torch.cat(parts)[:n].reshape(c.shape).to(t.device)
 
 
-def gather_bands(band, y0: int, y1: int, height: int, group=None):
-    """Stitch row-band films (with halos) into the full film on rank 0."""
+def stitch_bands(parts, bands, height: int, border: int):
+    """The full film, (height + 2 border) rows, from row-band films: part i
+    holds film rows [y0_i - border, y1_i + border) of band (y0_i, y1_i) =
+    bands[i] in its first y1_i - y0_i + 2 border rows (further rows are
+    padding). Neighbouring bands overlap in 2 border rows, which add up in
+    band order; with border 0 (box filter) the bands simply abut."""
+    import torch
+
+    b = int(border)
+    p0 = parts[0]
+    full = torch.zeros((height + 2 * b, p0.shape[1], p0.shape[2]), dtype=p0.dtype, device=p0.device)
+    for p, (y0, y1) in zip(parts, bands):
+        y0, y1 = int(y0), int(y1)
+        full[y0: y1 + 2 * b] += p[: y1 - y0 + 2 * b]
+    return full
+
+
+def gather_bands(band, y0: int, y1: int, height: int, group=None, border: int | None = None):
+    """Stitch row-band films (with halos) into the full film on rank 0.
+    `border`: the border of the films' reconstruction filter (None: read off
+    the band's own row count, rows = y1 - y0 + 2 border)."""
     import torch
     import torch.distributed as dist
 
     t = _to_tensor(band)
     world = dist.get_world_size(group)
     W2 = t.shape[1]
-    maxrows = max(b1 - b0 for b0, b1 in row_bands(height, world)) + 2
+    b = (t.shape[0] - (y1 - y0)) // 2 if border is None else int(border)
+    if b < 0 or t.shape[0] != y1 - y0 + 2 * b:
+        raise ValueError(f"a band film of rows [{y0}, {y1}) with border {b} has {y1 - y0 + 2 * b} rows, not {t.shape[0]}")
+    maxrows = max(b1 - b0 for b0, b1 in row_bands(height, world)) + 2 * b
     dev = t.device
     t = _comm(t, group)
     buf = torch.zeros((maxrows, W2, t.shape[2]), dtype=t.dtype, device=t.device)
@@ -166,11 +189,7 @@ def gather_bands(band, y0: int, y1: int, height: int, group=None):
     dist.all_gather(metas, meta, group=group)
     if dist.get_rank(group) != 0:
         return None
-    full = torch.zeros((height + 2, W2, t.shape[2]), dtype=t.dtype, device=t.device)
-    for p, m in zip(parts, metas):
-        a, b = int(m[0]), int(m[1])
-        full[a: b + 2] += p[: b - a + 2]
-    return full.to(dev)
+    return stitch_bands(parts, [(int(m[0]), int(m[1])) for m in metas], height, b).to(dev)
 
 
 def render_sharded(render, height: int, spp: int, mode: str = "samples", group=None):
@@ -249,7 +268,8 @@ def exchange_halos(export_rows, import_rows, y0: int, y1: int, height: int, halo
 
 def restir_band_frame(integ, scene, seed: int, y0: int, y1: int, exchange, spp: int = 1, out=None, ctx=None):
     """One ReSTIR GI frame for rows [y0, y1): stage A, exchange(), stage B.
-    Returns the band film (rows y0-1 .. y1)."""
+    Returns the band film (rows y0-b .. y1+b-1, b the border of the
+    integrator's reconstruction filter: 1 for the default tent)."""
     integ.render_film(scene, seed=seed, spp=spp, y0=y0, y1=y1, stage="A", ctx=ctx)
     exchange()
     return integ.render_film(scene, seed=seed, spp=spp, y0=y0, y1=y1, stage="B", out=out, ctx=ctx)

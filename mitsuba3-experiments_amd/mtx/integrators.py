@@ -57,9 +57,23 @@ class IndependentSampler:
         self.skip = int(skip)
 
 
-def develop(film: np.ndarray) -> np.ndarray:
-    """hdrfilm develop: inner W x H pixels, RGB / weight (0 where weight is 0)."""
-    inner = film[1:-1, 1:-1]
+def rfilter_border(rfilter) -> int:
+    """Border (pixels on every side of the raw film) of a reconstruction
+    filter given by name or MTX_RFILTER_* id: tent 1, box 0, gaussian 2."""
+    fid = _abi.RFILTERS.get(rfilter, rfilter)
+    if fid not in _abi.RFILTER_BORDER:
+        raise MtxError(f"unknown reconstruction filter {rfilter!r}; supported: {sorted(_abi.RFILTERS)}")
+    return _abi.RFILTER_BORDER[fid]
+
+
+def develop(film: np.ndarray, border: int = 1) -> np.ndarray:
+    """hdrfilm develop: inner W x H pixels, RGB / weight (0 where weight is 0).
+    `border` is the raw film's border (:func:`rfilter_border`: 1 for the
+    default tent); 0 crops nothing."""
+    border = int(border)
+    if border < 0 or 2 * border >= min(film.shape[0], film.shape[1]):
+        raise MtxError(f"border {border} does not fit a film of shape {tuple(film.shape)}")
+    inner = film[border: film.shape[0] - border, border: film.shape[1] - border]
     w = inner[..., 3:4]
     return np.where(w != 0, inner[..., :3] / np.where(w != 0, w, 1), 0).astype(np.float32)
 
@@ -90,11 +104,31 @@ class SamplingIntegrator:
 
     def __init__(self, props=None):
         self.props = Properties(props or {})
+        # The film's reconstruction filter: "tent" (the default, whatever the
+        # scene declares), "box", "gaussian", or "scene" = the filter the
+        # scene's film declares (Scene.rfilter).
+        self.rfilter = self.props.get("rfilter", "tent")
 
     # ------------------------------------------------------------ arguments --
+    def rfilter_id(self, scene, rfilter=None) -> int:
+        """MTX_RFILTER_* id a render of `scene` uses: `rfilter` ("tent",
+        "box", "gaussian" or "scene"), or the integrator's ``rfilter``
+        property when None. "scene" with a declared filter outside the three
+        raises MtxError rather than rendering with another one."""
+        name = self.rfilter if rfilter is None else rfilter
+        if name == "scene":
+            name = getattr(scene, "rfilter", "tent")
+            if name not in _abi.RFILTERS:
+                raise MtxError(f"the scene's film declares the reconstruction filter {name!r}; supported: "
+                               f"{sorted(_abi.RFILTERS)} (pass rfilter= one of them to override)")
+        if name not in _abi.RFILTERS:
+            raise MtxError(f"unknown reconstruction filter {name!r}; supported: {sorted(_abi.RFILTERS)} or 'scene'")
+        return _abi.RFILTERS[name]
+
     def render_args(self, scene, seed: int, spp: int, y0: int = 0, y1: int | None = None, spp_total: int | None = None,
-                    sample_offset: int = 0, chunk_paths: int = 0, flags: int = 0) -> _abi.RenderArgs:
+                    sample_offset: int = 0, chunk_paths: int = 0, flags: int = 0, rfilter=None) -> _abi.RenderArgs:
         a = _abi.RenderArgs()
+        a.rfilter = self.rfilter_id(scene, rfilter)
         a.integrator = self.integrator_id
         a.max_depth = int(self.max_depth)
         a.rr_depth = int(getattr(self, "rr_depth", 0))
@@ -114,8 +148,10 @@ class SamplingIntegrator:
     def render_film(self, scene, seed: int = 0, spp: int = 1, y0: int = 0, y1: int | None = None,
                     spp_total: int | None = None, sample_offset: int = 0, device: int | None = None,
                     out=None, stats: bool = False, chunk_paths: int = 0, counters: bool = False, ctx=None,
-                    extra_flags: int = 0, sensor=None):
-        """Raw film (rows y0-1..y1, cols -1..W) x RGBW. `out` may be a
+                    extra_flags: int = 0, sensor=None, rfilter=None):
+        """Raw film (rows y0-b..y1+b-1, cols -b..W+b-1) x RGBW, b the border of
+        the reconstruction filter (`rfilter`: see :meth:`rfilter_id`; tent, the
+        default: 1, box: 0, gaussian: 2). `out` may be a
         device tensor (torch, on the context's device) to keep the film in HBM.
         stats=True returns (film, stats) with per-kernel-class HIP-event
         times; counters=True also collects the traversal visit counters
@@ -125,9 +161,10 @@ class SamplingIntegrator:
         scene = scene_with_sensor(scene, sensor)
         _bind_scene(ctx, scene)
         a = self.render_args(scene, seed, spp, y0, y1, spp_total, sample_offset, chunk_paths,
-                             flags=(2 if stats else 0) | (1 if stats and counters else 0))
+                             flags=(2 if stats else 0) | (1 if stats and counters else 0), rfilter=rfilter)
         a.restir_flags |= int(extra_flags)
-        shape = (a.y1 - a.y0 + 2, scene.width + 2, 4)
+        b = rfilter_border(a.rfilter)
+        shape = (a.y1 - a.y0 + 2 * b, scene.width + 2 * b, 4)
         st = _abi.Stats()
         if out is None:
             film = np.zeros(shape, np.float32)
@@ -139,12 +176,13 @@ class SamplingIntegrator:
             check(lib().mtx_render(ctx.handle, C.byref(a), C.c_void_p(out.data_ptr()), 1, C.byref(st)), "mtx_render")
         return (film, st.as_dict()) if stats else film
 
-    def render(self, scene, sensor=None, seed: int = 0, spp: int = 1, develop: bool = True, evaluate: bool = True):
+    def render(self, scene, sensor=None, seed: int = 0, spp: int = 1, develop: bool = True, evaluate: bool = True,
+               rfilter=None):
         """SamplingIntegrator.render (path.py:103-192) through `sensor` (the
         scene's own when None / 0, as mi.render does; testpssmlt.py:45 passes
         scene.sensors()[0]): TensorXf[H, W, 3] of the sensor's film."""
-        film = self.render_film(scene, seed=seed, spp=spp, sensor=sensor)
-        return globals()["develop"](film) if develop else film
+        film = self.render_film(scene, seed=seed, spp=spp, sensor=sensor, rfilter=rfilter)
+        return globals()["develop"](film, rfilter_border(self.rfilter_id(scene, rfilter))) if develop else film
 
     # --------------------------------------------------------------- sample --
     def sample(self, scene, sampler: IndependentSampler, ray, medium=None, active=True):
@@ -163,7 +201,7 @@ class SamplingIntegrator:
             raise MtxError("sampler lanes and rays differ in length")
         ctx = context()
         _bind_scene(ctx, scene)
-        a = self.render_args(scene, sampler.seed, 1)
+        a = self.render_args(scene, sampler.seed, 1, rfilter="tent")  # sample() writes no film
         L = np.zeros((n, 3), np.float32)
         valid = np.zeros(n, np.uint8)
         check(lib().mtx_sample_rays(ctx.handle, C.byref(a), n, rays.ctypes.data, sampler.lanes.ctypes.data,
@@ -197,7 +235,7 @@ class SamplingIntegrator:
         valid = torch.empty(n, dtype=torch.uint8, device=dev)
         ctx = context(dev.index if dev.index is not None else torch.cuda.current_device())
         _bind_scene(ctx, scene)
-        a = self.render_args(scene, sampler.seed, 1)
+        a = self.render_args(scene, sampler.seed, 1, rfilter="tent")  # sample() writes no film
         torch.cuda.current_stream(dev).synchronize()  # libmtx runs on its own stream
         check(lib().mtx_sample_rays_dev(ctx.handle, C.byref(a), n, rays.data_ptr(), lanes.data_ptr(), sampler.skip,
                                         L.data_ptr(), valid.data_ptr()), "mtx_sample_rays_dev")
@@ -428,7 +466,7 @@ class RestirIntegrator(SamplingIntegrator):
 
     def render_film(self, scene, seed: int = 0, spp: int = 1, device: int | None = None, out=None,
                     stats: bool = False, counters: bool = False, y0: int = 0, y1: int | None = None,
-                    stage: str | None = None, ctx=None, sensor=None, **kwargs):
+                    stage: str | None = None, ctx=None, sensor=None, rfilter=None, **kwargs):
         """One frame (restirgi.py:182-258) through `sensor` (None: the
         scene's camera); advances the frame counter. The previous frame's
         camera is the context's prev_sensor (restirgi.py:226-227, :247).
@@ -457,7 +495,7 @@ class RestirIntegrator(SamplingIntegrator):
         self._ctx = ctx  # _bind_scene pointed the device camera at this frame's sensor
         flags = {None: 0, "A": _abi.MTX_RESTIR_STAGE_A, "B": _abi.MTX_RESTIR_STAGE_B}[stage]
         result = super().render_film(scene, seed=seed, spp=spp, device=device, out=out, stats=stats,
-                                     counters=counters, y0=y0, y1=y1, ctx=ctx, extra_flags=flags)
+                                     counters=counters, y0=y0, y1=y1, ctx=ctx, extra_flags=flags, rfilter=rfilter)
         if stage != "A":
             self.n += 1  # restirgi.py:245
         return result

@@ -45,6 +45,9 @@ class Scene:
     def __init__(self):
         self.meta = {}
         self.env_radiance = None  # constant environment radiance (rgb) or None
+        # the film's declared reconstruction filter (the spec's rfilter type; the
+        # bedroom's is "tent"). Renders use it only when asked: rfilter="scene".
+        self.rfilter = "tent"
 
     # ------------------------------------------------------------ building --
     @classmethod
@@ -267,8 +270,9 @@ class Scene:
         env = spec.get("environment")
         s.env_radiance = None if env is None else tuple(float(x) for x in _rgb3(env["radiance"]))
         s._build_bvh(tri_vidx, tri_shape)
+        s.rfilter = str(film.get("rfilter") or "tent")
         s.meta = {"scene": "bedroom-proxy" if not loaded else "xml", "proxy_version": proxy.PROXY_VERSION,
-                  "fov_axis": spec["sensor"].get("fov_axis", "x"),
+                  "fov_axis": spec["sensor"].get("fov_axis", "x"), "rfilter": s.rfilter,
                   "scale": scale, "width": W, "height": H, "n_tris": int(s.n_tris), "budgets": budgets,
                   "bvh_depth": s.bvh_depth, "n_nodes": int(s.n_nodes), "occ_depth": s.occ_depth,
                   "n_occ_nodes": int(s.n_occ_nodes), "loaded_files": loaded}
@@ -435,6 +439,7 @@ class Scene:
         s.textures = arr(_abi.Texture, z["textures"])
         s.camera = _abi.Camera.from_buffer_copy(z["camera"].tobytes())
         s.meta = json.loads(z["meta"].tobytes().decode())
+        s.rfilter = str(s.meta.get("rfilter", "tent"))
         (s.n_tris, s.n_nodes, s.n_textures, s.n_tables, s.bvh_depth, s.n_occ_nodes,
          s.occ_depth) = (int(x) for x in z["counts"])
         env = z["env"] if "env" in z.files else np.zeros(4, np.float32)
