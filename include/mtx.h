@@ -315,6 +315,23 @@ int mtx_bvh_build(const float *vpos, uint32_t n_verts, const uint32_t *tri_vidx,
  * occlusion leaf order -> input record; depth_out: levels of the tree. */
 int mtx_bvh_build_occlusion(const float *tri_geom, uint32_t n_tris, int32_t *nodes_out, uint32_t *n_nodes_out,
                             float *tri_geom_out, uint32_t *perm_out, uint32_t *depth_out);
+/* Host-only refit of the closest-hit tree after a vertex update (the host
+ * half of assigning vertex_positions and calling params.update() on
+ * mi.traverse of a scene): topology, leaf order and slot order stay; origins,
+ * exponents and the 8-bit child bounds of `nodes` (n_nodes nodes, in place)
+ * are recomputed bottom-up from the new vertices exactly as the builder
+ * computes them, so unchanged vertices give back the builder's nodes bit for
+ * bit. tri_vidx is in leaf order (the scene's); tri_geom_out: 12*n_tris
+ * floats, the new records. A non-finite coordinate, or one of magnitude above
+ * 2^37 (the bound under which quantisation with exponents <= 31 provably
+ * succeeds, mtx_core/geometry.h), is MTX_E_ARG and nothing is written. */
+int mtx_bvh_refit(const float *vpos, uint32_t n_verts, const uint32_t *tri_vidx, uint32_t n_tris,
+                  int32_t *nodes, uint32_t n_nodes, float *tri_geom_out);
+/* The same for the occlusion tree: tri_geom are the new records in scene
+ * order, occ_perm the scene triangle of each occlusion leaf-order triangle;
+ * occ_tri_geom_out: the records copied bit for bit through occ_perm. */
+int mtx_bvh_refit_occlusion(const float *tri_geom, const uint32_t *occ_perm, uint32_t n_tris,
+                            int32_t *occ_nodes, uint32_t n_occ_nodes, float *occ_tri_geom_out);
 /* Host-only roughplastic precompute (upstream roughplastic constructor):
  * external transmittance table (64 floats) and internal reflectance. */
 int mtx_roughplastic_tables(uint32_t distribution, float alpha, float eta, float *table_out,
@@ -322,6 +339,36 @@ int mtx_roughplastic_tables(uint32_t distribution, float alpha, float eta, float
 /* Copy a scene to HBM (replaces mi.load_file / mi.load_dict scene
  * construction, path.py:308-309, restirgi.py:599). */
 int mtx_scene_upload(mtx_ctx *ctx, const mtx_scene_desc *scene);
+/* New vertex positions for the uploaded scene, without a re-upload: the
+ * device half of assigning vertex_positions and calling params.update() on
+ * mi.traverse of a scene (test-restir-dynamic.py does the same for the sensor;
+ * see mtx_set_camera). vpos: 3*n_verts floats, n_verts as uploaded; vnormal:
+ * 3*n_verts floats or NULL (the normals are kept); on_device != 0: both are
+ * device memory of the context's device (the caller orders their producer
+ * before the call), else host memory. Topology, leaf order and slot order
+ * stay: the 36-byte triangle records of both trees, the position (and
+ * normal) rows of the shading records, vpos / vnormal, both trees' quantised
+ * child boxes and the environment's bounding sphere are rewritten in place on
+ * the context's stream, complete on return, and equal what mtx_bvh_refit /
+ * mtx_bvh_refit_occlusion and a fresh upload would give, bit for bit. Device
+ * pointers of the scene do not move. A read-only pre-pass refuses
+ * (MTX_E_ARG, scene untouched) a wrong vertex count, a non-finite coordinate
+ * or one of magnitude above 2^37, and any change to a triangle of an emitter
+ * shape (area emitters are held analytically in the emitter records; moving their
+ * triangles would split emitter sampling from traversal). Neural-radiosity
+ * surface tables are dropped as by an upload. ReSTIR GI reservoirs are kept:
+ * the reference has no reprojection under moving geometry either, so a caller
+ * restarts with frame = 0 or accepts stale reuse. Should a refit pass fail
+ * after the pre-pass, the scene is dropped (MTX_E_NOSCENE until the next
+ * upload) and an error returned: no half-refit tree stays live. */
+int mtx_scene_update_vertices(mtx_ctx *ctx, const float *vpos, const float *vnormal, uint32_t n_verts,
+                              int on_device);
+/* Read back one device array of the uploaded scene (test / debugging hook):
+ * which = 0 nodes, 1 occ_nodes (the ABI's words), 2 the closest-hit tree's
+ * triangles and 3 the occlusion tree's (9 floats each: v0, e1, e2), 4 the
+ * shading records (32 floats per triangle), 5 vpos, 6 vnormal, 7 the
+ * environment's bounding sphere (centre.xyz, radius). n_bytes must match. */
+int mtx_scene_read(mtx_ctx *ctx, int which, void *out, uint64_t n_bytes);
 
 /* --------------------------- integrators -------------------------- */
 /* Render film rows [y0,y1) plus the border b of args->rfilter into

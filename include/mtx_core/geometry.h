@@ -78,6 +78,71 @@ MTX_HD float wide_ldexp(float x, int e) {
 #endif
 }
 
+// ---- child-box quantisation (the builder and the refits, host and device) --
+// Every child box of both trees is pad(exact fp32 union of the child's
+// triangles' boxes), quantised in the frame of the union of the node's padded
+// child boxes. bvh_build.cpp, the host refit and the device refit (refit.hip)
+// all go through these three functions, so a refit with unchanged vertices
+// gives back the builder's nodes bit for bit.
+constexpr int kQuantEMin = -32, kQuantEMax = 31;  // int8 axis exponents of mtx.h
+// Largest |coordinate| a refit accepts: 2^(kQuantEMax + 6). A padded bound is
+// then below 2^37 (1 + 2^-17), a node's extent below 2^38 (1 + 2^-17), and the
+// widest frame reaches origin + 255 * 2^kQuantEMax > -2^37.01 + 2^38.99 >
+// 2^37.01 in fp32: the exponent search below always ends with
+// decode(origin, e, 255) >= the union's upper bound, so q_lo = 0 / q_hi = 255
+// are always admissible and quantise_bounds cannot fail.
+constexpr float kRefitMaxCoord = 137438953472.f;  // 2^37
+
+// Conservative padding: the slab test computes t = fma(b, 1/d, -o/d) with
+// |error| <= (|o| + |b|) |1/d| 2^-23 for points inside the scene, so a pad
+// of (|x| + E) 2^-19 (E = largest |coordinate| of the scene) covers it
+// with a 10x margin and no closest hit can be culled.
+// Contraction: (|x| + E) * 2^-19 is a scaling by a power of two and therefore
+// exact (unless it is subnormal, i.e. |x| + E < 2^-107), so x -+ that product
+// rounds once whether or not the compiler fuses it into an fma: host and
+// device give the same bits. The library is built with -ffp-contract=off in
+// any case.
+MTX_HD void pad_bounds(float *lo, float *hi, float extent) {
+  const float k = 1.0f / 524288.0f;  // 2^-19
+  *lo -= (fabsf(*lo) + extent) * k;
+  *hi += (fabsf(*hi) + extent) * k;
+}
+
+// Axis exponent of a node whose padded children span [ulo, uhi]: the smallest
+// e >= that of extent / 255 (clamped to the int8 field's range) whose frame
+// reaches uhi; the frame's origin is ulo.
+MTX_HD int quantise_exponent(float ulo, float uhi) {
+  const double ext = (double)uhi - (double)ulo;
+  int e = kQuantEMin;
+  if (ext > 0.0) {
+    // frexp's exponent of ext / 255 (a normal double: ext >= 2^-149)
+    const double x = ext / 255.0;
+    const int ee = (int)((__builtin_bit_cast(uint64_t, x) >> 52) & 0x7ffu) - 1022;
+    e = ee < kQuantEMin ? kQuantEMin : (ee > kQuantEMax ? kQuantEMax : ee);
+  }
+  while (e < kQuantEMax && wide_decode(ulo, wide_scale((uint32_t)(e & 255)), 255u) < uhi) ++e;
+  return e;
+}
+
+// Conservative 8-bit bounds of [lo, hi] in the frame (org, 2^e): first guess
+// in double, then stepped until the fp32 decode the traversal evaluates
+// contains the box. False when no byte does (a frame that does not reach).
+MTX_HD bool quantise_bounds(float org, int e, float lo, float hi, uint32_t *qlo_out, uint32_t *qhi_out) {
+  const float sc = wide_scale((uint32_t)(e & 255));
+  const double dsc = __builtin_bit_cast(double, (uint64_t)(e + 1023) << 52);  // 2^e
+  double flo = floor(((double)lo - (double)org) / dsc);
+  double fhi = ceil(((double)hi - (double)org) / dsc);
+  flo = flo < 255.0 ? flo : 255.0;
+  fhi = fhi < 255.0 ? fhi : 255.0;
+  uint32_t qlo = (uint32_t)(0.0 < flo ? flo : 0.0);
+  uint32_t qhi = (uint32_t)(0.0 < fhi ? fhi : 0.0);
+  while (qlo > 0 && wide_decode(org, sc, qlo) > lo) --qlo;
+  while (qhi < 255 && wide_decode(org, sc, qhi) < hi) ++qhi;
+  *qlo_out = qlo;
+  *qhi_out = qhi;
+  return !(wide_decode(org, sc, qlo) > lo || wide_decode(org, sc, qhi) < hi);
+}
+
 // ---- 4-wide sorted nodes (closest hit; layout MTX_BVH4 in mtx.h) --------
 // Slab tests of a node's children in the node's quantised frame: with
 // a = 2^e / d and b = (origin - o) / d per axis, a bound q is at

@@ -44,13 +44,20 @@ MTX_HD uint32_t emitter_count(const SceneView &s) { return s.n_emitters + (s.has
 
 // ConstantBackgroundEmitter::set_scene: the bounding sphere of the scene's
 // bounding box (centre, |centre - min|), its radius grown by a ray epsilon.
+// env_bsphere_box takes the box of all vertices (an empty or NaN box is
+// invalid): the host loop below and the device reduction of a vertex update
+// (refit.hip) share the formula.
+MTX_HD void env_bsphere_box(V3 lo, V3 hi, float center[3], float *radius);
 MTX_HD void env_bsphere(const float *vpos, uint32_t n_verts, float center[3], float *radius) {
   V3 lo = v3s(kInf), hi = v3s(-kInf);
   for (uint32_t i = 0; i < n_verts; ++i) {
     lo = V3{fminf(lo.x, vpos[3 * i]), fminf(lo.y, vpos[3 * i + 1]), fminf(lo.z, vpos[3 * i + 2])};
     hi = V3{fmaxf(hi.x, vpos[3 * i]), fmaxf(hi.y, vpos[3 * i + 1]), fmaxf(hi.z, vpos[3 * i + 2])};
   }
-  if (n_verts == 0 || !(lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z)) {  // invalid box
+  env_bsphere_box(lo, hi, center, radius);
+}
+MTX_HD void env_bsphere_box(V3 lo, V3 hi, float center[3], float *radius) {
+  if (!(lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z)) {  // invalid box
     center[0] = center[1] = center[2] = 0.f;
     *radius = kRayEpsilon;
     return;

@@ -23,6 +23,7 @@
 #include "mtx_core/film.h"
 #include "mtx_core/interaction.h"
 #include "prims.h"
+#include "refit.h"
 #include "wavefront.h"
 
 static thread_local char g_err[1024] = "";
@@ -135,6 +136,15 @@ struct mtx_ctx {
   DevBuf nr_lhs, nr_qp, nr_qd, nr_Lrhs, nr_lanes;
   DevBuf nodes, tri, occ_nodes, occ_tri, tri_vidx, tri_shape, vpos, vnormal, vuv, shapes, materials, emitters, textures, texels, tables;
   mtxd::DevScene scene{};
+  // vertex updates (mtx_scene_update_vertices): the occlusion tree's leaf
+  // order -> scene triangle, and the levels of both trees: level l is nodes
+  // [first[l], first[l + 1]) -- the builder's breadth-first layout -- or, for
+  // trees whose levels are not contiguous, those entries of the device list.
+  // The scratch (staged input, triangle and node boxes) is allocated by the
+  // first update, not by upload.
+  DevBuf occ_perm, lvl4_list, lvl8_list, rf_state, rf_tbox, rf_nbox, rf_vpos, rf_vnormal;
+  std::vector<uint32_t> lvl4_first, lvl8_first;
+  uint32_t scene_n_nodes = 0, scene_n_occ = 0, scene_n_verts = 0;
   // wavefront
   DevBuf ray_o, ray_d, thr, L, prev, misc, pos, hit, q0, q1, shadow, counters, stats;
   DevBuf xheads, rs_heads;  // per-XCD claim cursors of the persistent trace kernels
@@ -276,7 +286,9 @@ void mtx_ctx_destroy(mtx_ctx *c) {
                     &c->field_w16, &c->tr_p, &c->tr_m, &c->tr_v, &c->tr_g, &c->tr_wpart, &c->tr_loss, &c->tr_out,
                     &c->tr_dfeat, &c->tr_feat, &c->tr_flag, &c->tr_target, &c->nr_shape_pmf, &c->nr_shape_cdf,
                     &c->nr_tri_off, &c->nr_tri_pmf, &c->nr_tri_cdf, &c->nr_tri_prim, &c->nr_dists, &c->nr_lhs,
-                    &c->nr_qp, &c->nr_qd, &c->nr_Lrhs, &c->nr_lanes};
+                    &c->nr_qp, &c->nr_qd, &c->nr_Lrhs, &c->nr_lanes,
+                    &c->occ_perm, &c->lvl4_list, &c->lvl8_list, &c->rf_state, &c->rf_tbox, &c->rf_nbox, &c->rf_vpos,
+                    &c->rf_vnormal};
   for (DevBuf *b : bufs) dfree(*b);
   Wave2 &w = c->w2;
   for (DevBuf *b : {&w.ray_o, &w.ray_d, &w.thr, &w.L, &w.prev, &w.misc, &w.pos, &w.hit, &w.q0, &w.q1, &w.shadow,
@@ -351,6 +363,38 @@ static int occ_match(const mtx_scene_desc *d, std::vector<uint32_t> &perm) {
   return MTX_OK;
 }
 
+// Levels of a tree from its nodes' levels (0xffffffff: unreachable): level l
+// = [first[l], first[l + 1]). The builder lays both trees out breadth-first,
+// so a level is a contiguous node range and no list is kept; for any other
+// tree `list` holds the reachable nodes grouped by level.
+static int upload_levels(const std::vector<uint32_t> &level, uint32_t depth, std::vector<uint32_t> &first,
+                         DevBuf &list, hipStream_t st) {
+  first.assign((size_t)depth + 1, 0u);
+  bool contiguous = true;
+  uint32_t prev = 0;
+  for (uint32_t l : level) {
+    if (l >= depth) {
+      contiguous = false;
+      continue;
+    }
+    ++first[l + 1];
+    contiguous = contiguous && l >= prev;
+    prev = l;
+  }
+  for (uint32_t l = 0; l < depth; ++l) first[l + 1] += first[l];
+  if (contiguous) {
+    dfree(list);
+    return MTX_OK;
+  }
+  std::vector<uint32_t> idx(first[depth]), cursor(first.begin(), first.end() - 1);
+  for (size_t i = 0; i < level.size(); ++i)
+    if (level[i] < depth) idx[cursor[level[i]]++] = (uint32_t)i;
+  int rc = upload(list, idx.data(), idx.size(), st);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(st));  // idx is freed at scope exit
+  return MTX_OK;
+}
+
 int mtx_scene_upload(mtx_ctx *c, const mtx_scene_desc *d) {
   if (!c || !d) {
     mtx_set_error("mtx_scene_upload: null argument");
@@ -377,8 +421,9 @@ int mtx_scene_upload(mtx_ctx *c, const mtx_scene_desc *d) {
   if (!occ_given) {
     occ_nodes_v.resize(((size_t)d->n_tris + 1) * MTX_OCC_NODE_WORDS);
     occ_geom_v.resize(12 * (size_t)d->n_tris);
+    occ_perm_v.resize(d->n_tris);
     if ((rc = mtx_bvh_build_occlusion(d->tri_geom, d->n_tris, occ_nodes_v.data(), &n_occ, occ_geom_v.data(),
-                                      nullptr, nullptr)))
+                                      occ_perm_v.data(), nullptr)))
       return rc;
     occ_nodes = occ_nodes_v.data();
     occ_geom = occ_geom_v.data();
@@ -390,12 +435,15 @@ int mtx_scene_upload(mtx_ctx *c, const mtx_scene_desc *d) {
   // at most 3 node references, an 8-wide level one node group); also
   // rejects cycles.
   uint32_t bvh_depth = 0, occ_depth = 0;
+  // level of every reachable node (vertex updates refit level by level)
+  std::vector<uint32_t> level4(d->n_nodes, 0xffffffffu), level8(n_occ, 0xffffffffu);
   {
     std::vector<std::pair<int32_t, uint32_t>> todo{{0, 0u}};
     uint64_t visited = 0;
     while (!todo.empty()) {
       auto [nd, dep] = todo.back();
       todo.pop_back();
+      level4[nd] = dep;
       bvh_depth = std::max(bvh_depth, dep + 1);
       if (++visited > d->n_nodes || dep >= MTX_BVH_MAX_DEPTH) {
         mtx_set_error("mtx_scene_upload: BVH is not a tree of depth <= %d", MTX_BVH_MAX_DEPTH);
@@ -431,6 +479,7 @@ int mtx_scene_upload(mtx_ctx *c, const mtx_scene_desc *d) {
     while (!todo.empty()) {
       auto [nd, dep] = todo.back();
       todo.pop_back();
+      level8[nd] = dep;
       occ_depth = std::max(occ_depth, dep + 1);
       if (++visited > n_occ || dep >= MTX_BVH_MAX_DEPTH) {
         mtx_set_error("mtx_scene_upload: occlusion BVH is not a tree of depth <= %d", MTX_BVH_MAX_DEPTH);
@@ -509,6 +558,12 @@ int mtx_scene_upload(mtx_ctx *c, const mtx_scene_desc *d) {
     if ((rc = upload(tree ? c->occ_tri : c->tri, g9.data(), g9.size(), st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));  // g9 is freed at scope exit
   }
+  if ((rc = upload(c->occ_perm, occ_perm_v.data(), (size_t)d->n_tris, st))) return rc;
+  if ((rc = upload_levels(level4, bvh_depth, c->lvl4_first, c->lvl4_list, st))) return rc;
+  if ((rc = upload_levels(level8, occ_depth, c->lvl8_first, c->lvl8_list, st))) return rc;
+  c->scene_n_nodes = d->n_nodes;
+  c->scene_n_occ = n_occ;
+  c->scene_n_verts = d->n_verts;
   if ((rc = upload(c->tri_vidx, d->tri_vidx, 3ull * d->n_tris, st))) return rc;
   if ((rc = upload(c->tri_shape, d->tri_shape, (size_t)d->n_tris, st))) return rc;
   if ((rc = upload(c->vpos, d->vpos, 3ull * d->n_verts, st))) return rc;
@@ -1632,6 +1687,151 @@ static int need_device(const mtx_ctx *c, const char *fn, std::initializer_list<c
     }
     ++k;
   }
+  return MTX_OK;
+}
+
+// New vertex positions for the uploaded scene (refit.hip). The pre-pass reads
+// only; a refusal leaves the scene as it was. After it every pass is
+// stream-ordered: triangles, the closest-hit tree's levels from the deepest
+// to the root, the occlusion records, the occlusion tree's levels.
+int mtx_scene_update_vertices(mtx_ctx *c, const float *vpos, const float *vnormal, uint32_t n_verts, int dev) {
+  if (!c || !vpos) {
+    mtx_set_error("mtx_scene_update_vertices: null argument");
+    return MTX_E_ARG;
+  }
+  if (!c->has_scene) {
+    mtx_set_error("no scene uploaded");
+    return MTX_E_NOSCENE;
+  }
+  if (n_verts != c->scene_n_verts) {
+    mtx_set_error("mtx_scene_update_vertices: %u vertices given, the scene has %u (topology changes need a new upload)",
+                  n_verts, c->scene_n_verts);
+    return MTX_E_ARG;
+  }
+  if (vnormal && !c->vnormal.p) {
+    mtx_set_error("mtx_scene_update_vertices: the scene was uploaded without vertex normals");
+    return MTX_E_ARG;
+  }
+  int rc;
+  if (dev && (rc = need_device(c, "mtx_scene_update_vertices", {vpos, vnormal}))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const mtxd::DevScene &s = c->scene;
+  const uint32_t n_tris = s.n_tris;
+  const size_t vbytes = 12ull * n_verts;
+  if ((rc = dalloc(c->rf_state, mtxd::RF_WORDS * sizeof(uint32_t)))) return rc;
+  if ((rc = dalloc(c->rf_tbox, 24ull * n_tris))) return rc;
+  if ((rc = dalloc(c->rf_nbox, 24ull * std::max(c->scene_n_nodes, c->scene_n_occ)))) return rc;
+  const float *vp = vpos, *vn = vnormal;
+  if (!dev) {  // stage the host arrays: the scene's own copies stay until the checks pass
+    if ((rc = dalloc(c->rf_vpos, vbytes))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->rf_vpos.p, vpos, vbytes, hipMemcpyHostToDevice, st));
+    vp = (const float *)c->rf_vpos.p;
+    if (vnormal) {
+      if ((rc = dalloc(c->rf_vnormal, vbytes))) return rc;
+      HIP_TRY(hipMemcpyAsync(c->rf_vnormal.p, vnormal, vbytes, hipMemcpyHostToDevice, st));
+      vn = (const float *)c->rf_vnormal.p;
+    }
+  }
+  uint32_t *state = (uint32_t *)c->rf_state.p;
+  mtxd::refit_state_init(state, st);
+  mtxd::refit_prepass(vp, n_verts, s.tri_vidx, s.tri_shape, s.shapes, (const float *)c->shade_rec.p, n_tris, state, st);
+  uint32_t h[mtxd::RF_WORDS];
+  HIP_TRY(hipMemcpyAsync(h, state, sizeof(h), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  if (h[mtxd::RF_FLAGS] & mtxd::RF_BAD_COORD) {
+    mtx_set_error("mtx_scene_update_vertices: a coordinate is non-finite or beyond the magnitude bound 2^37; the "
+                  "scene is unchanged");
+    return MTX_E_ARG;
+  }
+  if (h[mtxd::RF_FLAGS] & mtxd::RF_BAD_EMITTER) {
+    mtx_set_error("mtx_scene_update_vertices: a vertex of an emitter shape would move (area emitters are held "
+                  "analytically and cannot be animated); the scene is unchanged");
+    return MTX_E_ARG;
+  }
+  // from here on the scene is written
+  if (vp != (const float *)c->vpos.p)
+    HIP_TRY(hipMemcpyAsync(c->vpos.p, vp, vbytes, hipMemcpyDeviceToDevice, st));
+  if (vn && vn != (const float *)c->vnormal.p)
+    HIP_TRY(hipMemcpyAsync(c->vnormal.p, vn, vbytes, hipMemcpyDeviceToDevice, st));
+  float *tbox = (float *)c->rf_tbox.p, *nbox = (float *)c->rf_nbox.p;
+  mtxd::refit_triangles(vp, vn, s.tri_vidx, n_tris, (float *)c->tri.p, (float *)c->shade_rec.p, tbox, st);
+  const float extent = mtx::u2f(h[mtxd::RF_EXTENT]), occ_extent = mtx::u2f(h[mtxd::RF_OCC_EXTENT]);
+  for (size_t l = c->lvl4_first.size() - 1; l-- > 0;)
+    mtxd::refit_level4((int32_t *)c->nodes.p, c->lvl4_first[l], c->lvl4_first[l + 1] - c->lvl4_first[l],
+                       (const uint32_t *)c->lvl4_list.p, tbox, nbox, extent, state, st);
+  mtxd::refit_occ_gather((const float *)c->tri.p, (const uint32_t *)c->occ_perm.p, n_tris, (float *)c->occ_tri.p, tbox,
+                         st);
+  for (size_t l = c->lvl8_first.size() - 1; l-- > 0;)
+    mtxd::refit_level8((uint32_t *)c->occ_nodes.p, c->lvl8_first[l], c->lvl8_first[l + 1] - c->lvl8_first[l],
+                       (const uint32_t *)c->lvl8_list.p, tbox, nbox, occ_extent, state, st);
+  uint32_t flags = 0;
+  hipError_t e = hipMemcpyAsync(&flags, state + mtxd::RF_FLAGS, sizeof(flags), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess || (flags & mtxd::RF_BAD_QUANT)) {
+    c->has_scene = false;  // never leave a half-refit tree live
+    if (e != hipSuccess) {
+      mtx_set_error("mtx_scene_update_vertices: %s; the scene was dropped, upload it again", hipGetErrorString(e));
+      return MTX_E_HIP;
+    }
+    mtx_set_error("mtx_scene_update_vertices: child box quantisation failed; the scene was dropped, upload it again");
+    return MTX_E_ARG;
+  }
+  mtx::V3 lo, hi;
+  lo.x = mtxd::refit_key_decode(h[mtxd::RF_LO]);
+  lo.y = mtxd::refit_key_decode(h[mtxd::RF_LO + 1]);
+  lo.z = mtxd::refit_key_decode(h[mtxd::RF_LO + 2]);
+  hi.x = mtxd::refit_key_decode(h[mtxd::RF_HI]);
+  hi.y = mtxd::refit_key_decode(h[mtxd::RF_HI + 1]);
+  hi.z = mtxd::refit_key_decode(h[mtxd::RF_HI + 2]);
+  mtx::env_bsphere_box(lo, hi, c->scene.env_center, &c->scene.env_radius);
+  c->has_nerad = false;  // surface tables belong to the previous geometry
+  // The ReSTIR GI reservoirs are kept: the reference has no reprojection under
+  // moving geometry either; a caller restarts with frame = 0 or accepts stale reuse.
+  return MTX_OK;
+}
+
+// Test / debugging hook: the device copy of one scene array.
+int mtx_scene_read(mtx_ctx *c, int which, void *out, uint64_t n_bytes) {
+  if (!c || !out) {
+    mtx_set_error("mtx_scene_read: null argument");
+    return MTX_E_ARG;
+  }
+  if (!c->has_scene) {
+    mtx_set_error("no scene uploaded");
+    return MTX_E_NOSCENE;
+  }
+  const uint64_t nt = c->scene.n_tris, nv = c->scene_n_verts;
+  const void *src = nullptr;
+  uint64_t need = 0;
+  switch (which) {
+    case 0: src = c->nodes.p; need = 4ull * MTX_BVH_NODE_WORDS * c->scene_n_nodes; break;
+    case 1: src = c->occ_nodes.p; need = 4ull * MTX_OCC_NODE_WORDS * c->scene_n_occ; break;
+    case 2: src = c->tri.p; need = 36 * nt; break;
+    case 3: src = c->occ_tri.p; need = 36 * nt; break;
+    case 4: src = c->shade_rec.p; need = 128 * nt; break;
+    case 5: src = c->vpos.p; need = 12 * nv; break;
+    case 6: src = c->vnormal.p; need = c->vnormal.p ? 12 * nv : 0; break;
+    case 7: need = 16; break;
+    default:
+      mtx_set_error("mtx_scene_read: which=%d not in 0..7", which);
+      return MTX_E_ARG;
+  }
+  if (n_bytes != need) {
+    mtx_set_error("mtx_scene_read: which=%d holds %llu bytes, got room for %llu", which, (unsigned long long)need,
+                  (unsigned long long)n_bytes);
+    return MTX_E_ARG;
+  }
+  if (which == 7) {
+    float sph[4] = {c->scene.env_center[0], c->scene.env_center[1], c->scene.env_center[2], c->scene.env_radius};
+    memcpy(out, sph, sizeof(sph));
+    return MTX_OK;
+  }
+  if (need == 0) return MTX_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpy(out, src, need, hipMemcpyDeviceToHost));
   return MTX_OK;
 }
 

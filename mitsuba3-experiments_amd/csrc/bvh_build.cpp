@@ -28,6 +28,7 @@
 #include "mtx_core/bsdf.h"
 #include "mtx_core/geometry.h"
 #include "mtx_core/microfacet.h"
+#include "mtx_core/refit.h"
 
 void mtx_set_error(const char *fmt, ...);
 
@@ -182,17 +183,12 @@ struct Builder {
     return m;
   }
 
-  // Conservative padding: the slab test computes t = fma(b, 1/d, -o/d) with
-  // |error| <= (|o| + |b|) |1/d| 2^-23 for points inside the scene, so a pad
-  // of (|x| + E) 2^-19 (E = largest |coordinate| of the scene) covers it
-  // with a 10x margin and no closest hit can be culled.
+  // Conservative padding by (|x| + extent) 2^-19 (mtx_core/geometry.h
+  // pad_bounds, shared with the refits); extent = largest |coordinate| of the
+  // referenced vertices.
   float extent = 0.f;
   void pad_box(Box &b) const {
-    const float k = 1.0f / 524288.0f;  // 2^-19
-    for (int a = 0; a < 3; ++a) {
-      b.lo[a] -= (std::fabs(b.lo[a]) + extent) * k;
-      b.hi[a] += (std::fabs(b.hi[a]) + extent) * k;
-    }
+    for (int a = 0; a < 3; ++a) mtx::pad_bounds(&b.lo[a], &b.hi[a], extent);
   }
 
   void store_child_boxes(uint32_t node, const Box &b0, const Box &b1) {
@@ -354,37 +350,19 @@ struct Builder {
   }
 
   bool quant_ok = true;
-  static constexpr int kEMin = -32, kEMax = 31;
   std::vector<int32_t> wnodes;  // the wide tree (16 or 20 words per node)
   uint32_t wide_depth = 0;
 
   // Quantisation of axis a of the children's boxes in the frame of their
-  // union: origin, exponent and the conservative 8-bit bounds of each child.
+  // union: origin, exponent and the conservative 8-bit bounds of each child
+  // (mtx_core/geometry.h quantise_exponent / quantise_bounds, shared with the
+  // refits).
   void quantise_axis(const std::vector<Child> &ch, const Box &u, int a, float *org_out, int *e_out,
                      uint32_t *qlo_out, uint32_t *qhi_out) {
     const float org = u.lo[a];
-    const double ext = (double)u.hi[a] - (double)org;
-    int e = kEMin;
-    if (ext > 0.0) {
-      int ee;
-      std::frexp(ext / 255.0, &ee);
-      e = std::max(kEMin, std::min(kEMax, ee));
-    }
-    while (e < kEMax && mtx::wide_decode(org, mtx::wide_scale((uint32_t)(e & 255)), 255u) < u.hi[a]) ++e;
-    const float sc = mtx::wide_scale((uint32_t)(e & 255));
-    const double dsc = std::ldexp(1.0, e);
-    for (size_t k = 0; k < ch.size(); ++k) {
-      double flo = std::floor(((double)ch[k].box.lo[a] - (double)org) / dsc);
-      double fhi = std::ceil(((double)ch[k].box.hi[a] - (double)org) / dsc);
-      uint32_t qlo = (uint32_t)std::max(0.0, std::min(255.0, flo));
-      uint32_t qhi = (uint32_t)std::max(0.0, std::min(255.0, fhi));
-      while (qlo > 0 && mtx::wide_decode(org, sc, qlo) > ch[k].box.lo[a]) --qlo;
-      while (qhi < 255 && mtx::wide_decode(org, sc, qhi) < ch[k].box.hi[a]) ++qhi;
-      if (mtx::wide_decode(org, sc, qlo) > ch[k].box.lo[a] || mtx::wide_decode(org, sc, qhi) < ch[k].box.hi[a])
-        quant_ok = false;
-      qlo_out[k] = qlo;
-      qhi_out[k] = qhi;
-    }
+    const int e = mtx::quantise_exponent(org, u.hi[a]);
+    for (size_t k = 0; k < ch.size(); ++k)
+      if (!mtx::quantise_bounds(org, e, ch[k].box.lo[a], ch[k].box.hi[a], &qlo_out[k], &qhi_out[k])) quant_ok = false;
     *org_out = org;
     *e_out = e;
   }
@@ -773,6 +751,178 @@ extern "C" int mtx_bvh_build_occlusion(const float *tri_geom, uint32_t n_tris, i
     std::memcpy(&tri_geom_out[12 * (size_t)i], &tri_geom[12 * (size_t)b.order[i]], 12 * sizeof(float));
   }
   if (depth_out) *depth_out = b.wide_depth;
+  return MTX_OK;
+}
+
+// --------------------------------------------------------------------------
+// refit (mtx_core/refit.h): new vertex positions under an unchanged topology
+// --------------------------------------------------------------------------
+
+namespace {
+
+// Nodes of a tree in breadth-first order from the root (children after their
+// parents in the list, whatever their indices), with every reference checked:
+// the refit walks the list backwards. kids(node, out) appends the inner
+// children and returns false on a malformed node.
+template <class Kids>
+int refit_order(uint32_t n_nodes, const char *fn, Kids kids, std::vector<uint32_t> &order) {
+  order.clear();
+  order.reserve(n_nodes);
+  order.push_back(0u);
+  std::vector<uint32_t> ch;
+  for (size_t qi = 0; qi < order.size(); ++qi) {
+    ch.clear();
+    if (!kids(order[qi], ch)) {
+      mtx_set_error("%s: node %u is malformed (child or triangle range out of bounds)", fn, order[qi]);
+      return MTX_E_ARG;
+    }
+    if (order.size() + ch.size() > n_nodes) {
+      mtx_set_error("%s: the nodes are not a tree of %u nodes", fn, n_nodes);
+      return MTX_E_ARG;
+    }
+    order.insert(order.end(), ch.begin(), ch.end());
+  }
+  return MTX_OK;
+}
+
+// Finite and within the refit's magnitude bound (geometry.h kRefitMaxCoord).
+bool refit_coord_ok(float x, float bound) { return std::fabs(x) <= bound; }  // false for NaN and inf
+
+}  // namespace
+
+extern "C" int mtx_bvh_refit(const float *vpos, uint32_t n_verts, const uint32_t *tri_vidx, uint32_t n_tris,
+                             int32_t *nodes, uint32_t n_nodes, float *tri_geom_out) {
+  if (!vpos || !tri_vidx || !nodes || !tri_geom_out || n_tris == 0 || n_nodes == 0 || n_verts == 0) {
+    mtx_set_error("mtx_bvh_refit: null argument or empty mesh");
+    return MTX_E_ARG;
+  }
+  for (uint64_t i = 0; i < 3ull * n_tris; ++i)
+    if (tri_vidx[i] >= n_verts) {
+      mtx_set_error("mtx_bvh_refit: vertex index %u out of range (%u vertices)", tri_vidx[i], n_verts);
+      return MTX_E_ARG;
+    }
+  for (uint64_t i = 0; i < 3ull * n_verts; ++i)
+    if (!refit_coord_ok(vpos[i], mtx::kRefitMaxCoord)) {
+      mtx_set_error("mtx_bvh_refit: vertex %llu has a non-finite coordinate or one beyond the magnitude bound 2^37 "
+                    "(%g)", (unsigned long long)(i / 3), (double)vpos[i]);
+      return MTX_E_ARG;
+    }
+  std::vector<uint32_t> order;
+  int rc = refit_order(n_nodes, "mtx_bvh_refit", [&](uint32_t nd, std::vector<uint32_t> &out) {
+    const int32_t *W = nodes + MTX_BVH_NODE_WORDS * (size_t)nd;
+    const uint32_t nch = (uint32_t)W[3] >> 24;
+    if (nch < 1 || nch > MTX_BVH_WIDTH) return false;
+    for (uint32_t k = 0; k < nch; ++k) {
+      if (W[4 + k] >= 0) {
+        if ((uint32_t)W[4 + k] >= n_nodes) return false;
+        out.push_back((uint32_t)W[4 + k]);
+      } else {
+        uint32_t first, cnt;
+        mtx::leaf_decode(W[4 + k], &first, &cnt);
+        if ((uint64_t)first + cnt > n_tris) return false;
+      }
+    }
+    return true;
+  }, order);
+  if (rc) return rc;
+  // nothing was written up to here
+  uint32_t ext_bits = 0;
+  std::vector<float> tbox(6 * (size_t)n_tris), nbox(6 * (size_t)n_nodes);
+  for (uint32_t t = 0; t < n_tris; ++t) {
+    const float *p[3];
+    for (int k = 0; k < 3; ++k) {
+      p[k] = &vpos[3 * (size_t)tri_vidx[3 * (size_t)t + k]];
+      for (int a = 0; a < 3; ++a) ext_bits = std::max(ext_bits, mtx::abs_bits(p[k][a]));
+    }
+    float *g = &tri_geom_out[12 * (size_t)t];
+    mtx::tri_record(p[0], p[1], p[2], g, g + 4, g + 8);
+    g[3] = g[7] = g[11] = 0.f;
+    float *b = &tbox[6 * (size_t)t];
+    mtx::box_reset(b);
+    for (int k = 0; k < 3; ++k) mtx::box_grow_point(b, p[k]);
+  }
+  const float extent = mtx::u2f(ext_bits);
+  bool ok = true;
+  for (size_t i = order.size(); i-- > 0;) {
+    const uint32_t nd = order[i];
+    ok = mtx::refit_node4(nodes + MTX_BVH_NODE_WORDS * (size_t)nd, tbox.data(), nbox.data(), extent,
+                          &nbox[6 * (size_t)nd]) && ok;
+  }
+  if (!ok) {  // cannot happen within the magnitude bound (geometry.h)
+    mtx_set_error("mtx_bvh_refit: child box quantisation failed");
+    return MTX_E_ARG;
+  }
+  return MTX_OK;
+}
+
+extern "C" int mtx_bvh_refit_occlusion(const float *tri_geom, const uint32_t *occ_perm, uint32_t n_tris,
+                                       int32_t *occ_nodes, uint32_t n_occ_nodes, float *occ_tri_geom_out) {
+  if (!tri_geom || !occ_perm || !occ_nodes || !occ_tri_geom_out || n_tris == 0 || n_occ_nodes == 0) {
+    mtx_set_error("mtx_bvh_refit_occlusion: null argument or empty mesh");
+    return MTX_E_ARG;
+  }
+  for (uint32_t i = 0; i < n_tris; ++i)
+    if (occ_perm[i] >= n_tris) {
+      mtx_set_error("mtx_bvh_refit_occlusion: occ_perm[%u] = %u out of range (%u triangles)", i, occ_perm[i], n_tris);
+      return MTX_E_ARG;
+    }
+  for (uint32_t t = 0; t < n_tris; ++t) {
+    const float *g = &tri_geom[12 * (size_t)t];
+    float pts[9];
+    mtx::occ_points(g, g + 4, g + 8, pts);
+    for (int j = 0; j < 9; ++j)
+      if (!refit_coord_ok(pts[j], mtx::kRefitMaxPoint)) {
+        mtx_set_error("mtx_bvh_refit_occlusion: triangle %u has a non-finite coordinate or one beyond the magnitude "
+                      "bound 2^37 (%g)", t, (double)pts[j]);
+        return MTX_E_ARG;
+      }
+  }
+  uint32_t *nodes = reinterpret_cast<uint32_t *>(occ_nodes);
+  std::vector<uint32_t> order;
+  int rc = refit_order(n_occ_nodes, "mtx_bvh_refit_occlusion", [&](uint32_t nd, std::vector<uint32_t> &out) {
+    const uint32_t *W = nodes + MTX_OCC_NODE_WORDS * (size_t)nd;
+    const uint32_t imask = W[3] >> 24, child_base = W[4], tri_base = W[5];
+    uint32_t inner = 0, any = 0;
+    for (uint32_t sl = 0; sl < MTX_OCC_WIDTH; ++sl) {
+      const uint32_t m = (W[6 + (sl >> 2)] >> (8 * (sl & 3))) & 0xffu;
+      if ((imask >> sl) & 1u) {
+        const uint64_t ch = (uint64_t)child_base + inner++;
+        if (ch >= n_occ_nodes) return false;
+        out.push_back((uint32_t)ch);
+        ++any;
+      } else if (m != 0) {
+        const uint32_t cb = m >> 5, cnt = cb == 1 ? 1u : cb == 3 ? 2u : cb == 7 ? 3u : 0u;
+        if (cnt == 0 || (uint64_t)tri_base + (m & 31u) + cnt > n_tris) return false;
+        ++any;
+      }
+    }
+    return any != 0;
+  }, order);
+  if (rc) return rc;
+  // nothing was written up to here
+  uint32_t ext_bits = 0;
+  std::vector<float> tbox(6 * (size_t)n_tris), nbox(6 * (size_t)n_occ_nodes);
+  for (uint32_t i = 0; i < n_tris; ++i) {
+    const float *g = &tri_geom[12 * (size_t)occ_perm[i]];
+    std::memcpy(&occ_tri_geom_out[12 * (size_t)i], g, 12 * sizeof(float));
+    float pts[9];
+    mtx::occ_points(g, g + 4, g + 8, pts);
+    float *b = &tbox[6 * (size_t)i];
+    mtx::box_reset(b);
+    for (int k = 0; k < 3; ++k) mtx::box_grow_point(b, pts + 3 * k);
+    for (int j = 0; j < 9; ++j) ext_bits = std::max(ext_bits, mtx::abs_bits(pts[j]));
+  }
+  const float extent = mtx::u2f(ext_bits);
+  bool ok = true;
+  for (size_t i = order.size(); i-- > 0;) {
+    const uint32_t nd = order[i];
+    ok = mtx::refit_node8(nodes + MTX_OCC_NODE_WORDS * (size_t)nd, tbox.data(), nbox.data(), extent,
+                          &nbox[6 * (size_t)nd]) && ok;
+  }
+  if (!ok) {  // cannot happen within the magnitude bound (geometry.h)
+    mtx_set_error("mtx_bvh_refit_occlusion: child box quantisation failed");
+    return MTX_E_ARG;
+  }
   return MTX_OK;
 }
 

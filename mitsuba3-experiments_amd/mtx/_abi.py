@@ -315,4 +315,8 @@ EXPORTS = [
     "mtx_nerad_step",
     "mtx_rfilter_info",
     "mtx_rfilter_eval",
+    "mtx_bvh_refit",
+    "mtx_bvh_refit_occlusion",
+    "mtx_scene_update_vertices",
+    "mtx_scene_read",
 ]

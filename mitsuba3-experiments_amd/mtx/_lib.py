@@ -89,6 +89,10 @@ def lib() -> C.CDLL:
         "mtx_nerad_step": ([vp, C.POINTER(_abi.NeradArgs), C.POINTER(_abi.TrainStats)], C.c_int),
         "mtx_rfilter_info": ([u32, C.POINTER(u32), C.POINTER(C.c_float)], C.c_int),
         "mtx_rfilter_eval": ([u32, vp, vp, u64], C.c_int),
+        "mtx_bvh_refit": ([vp, u32, vp, u32, vp, u32, vp], C.c_int),
+        "mtx_bvh_refit_occlusion": ([vp, vp, u32, vp, u32, vp], C.c_int),
+        "mtx_scene_update_vertices": ([vp, vp, vp, u32, C.c_int], C.c_int),
+        "mtx_scene_read": ([vp, C.c_int, vp, u64], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -124,10 +128,70 @@ class Context:
         self._h = h
         self.device = device
         self.scene = None
+        self.n_refits = 0  # vertex updates applied (update_vertices)
 
     @property
     def handle(self):
         return self._h
+
+    def update_vertices(self, vpos, vnormal=None) -> None:
+        """New vertex positions (and optionally normals) for the uploaded
+        scene without a re-upload (mtx_scene_update_vertices): assigning
+        ``vertex_positions`` and calling ``params.update()`` on
+        ``mi.traverse(scene)``. `vpos` / `vnormal`: (n_verts, 3) float32
+        numpy arrays, or torch CUDA tensors on this context's device (a
+        simulation that lives on the GPU: nothing passes through the host; the
+        tensors' producer is synchronised first). Topology stays; emitter
+        shapes must not move; MtxError with the reason otherwise, and the
+        device scene is then unchanged.
+
+        The host ``Scene`` this context was bound to is stale afterwards: the
+        context forgets it, so the next scene rendered through it is uploaded
+        in full. Make the matching host scene with ``Scene.with_vertices``
+        when one is needed (the oracle, another context)."""
+        import numpy as np
+
+        def prep(a):
+            if a is None:
+                return None, None, False
+            if hasattr(a, "data_ptr"):  # torch tensor
+                import torch
+                if not a.is_cuda or a.device.index != self.device:
+                    raise MtxError(f"update_vertices: tensor on {a.device}, the context is on cuda:{self.device}")
+                t = a.detach().to(torch.float32).contiguous().reshape(-1, 3)
+                torch.cuda.current_stream(t.device).synchronize()
+                return t, t.data_ptr(), True
+            h = np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+            return h, h.ctypes.data, False
+
+        p, pp, pdev = prep(vpos)
+        n, np_, ndev = prep(vnormal)
+        if n is not None and (ndev != pdev or len(n) != len(p)):
+            raise MtxError("update_vertices: vpos and vnormal must both be numpy arrays or both CUDA tensors, "
+                           "of one length")
+        self._scene_key = None
+        self._geom_token = None
+        self.scene = None
+        check(lib().mtx_scene_update_vertices(self._h, pp, np_, len(p), 1 if pdev else 0),
+              "mtx_scene_update_vertices")
+        self.n_refits += 1
+
+    def scene_read(self, which: str):
+        """The device copy of one scene array (mtx_scene_read; tests and
+        debugging): 'nodes', 'occ_nodes', 'tri', 'occ_tri', 'shade_rec',
+        'vpos', 'vnormal' or 'env_sphere'. `n_*` come from the bound scene."""
+        import numpy as np
+        names = ["nodes", "occ_nodes", "tri", "occ_tri", "shade_rec", "vpos", "vnormal", "env_sphere"]
+        s = getattr(self, "_read_counts", None)
+        if s is None:
+            raise MtxError("scene_read: no scene was bound to this context")
+        size = {"nodes": (16 * s["n_nodes"], np.int32), "occ_nodes": (20 * s["n_occ_nodes"], np.int32),
+                "tri": (9 * s["n_tris"], np.float32), "occ_tri": (9 * s["n_tris"], np.float32),
+                "shade_rec": (32 * s["n_tris"], np.float32), "vpos": (3 * s["n_verts"], np.float32),
+                "vnormal": (3 * s["n_verts"], np.float32), "env_sphere": (4, np.float32)}[which]
+        out = np.zeros(size[0], size[1])
+        check(lib().mtx_scene_read(self._h, names.index(which), out.ctypes.data, out.nbytes), "mtx_scene_read")
+        return out
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

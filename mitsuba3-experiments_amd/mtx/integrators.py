@@ -17,6 +17,7 @@ When ``mitsuba`` is importable the classes can additionally be registered as
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -574,7 +575,11 @@ def _bind_scene(ctx, scene) -> None:
     """Upload `scene` to the context's device once (keyed by its geometry and
     film size); a scene sharing the bound geometry and film size with another
     camera (Scene.with_camera, scene_with_sensor) only re-points the device
-    camera (mtx_set_camera)."""
+    camera (mtx_set_camera). A scene made from the bound one by
+    Scene.with_vertices (same geometry-base token and film size, other node
+    arrays) is not uploaded either: its vertices go through
+    mtx_scene_update_vertices, which refits both trees on the device
+    (MTX_REFIT_UPLOAD=1 forces the full upload, for A/B runs)."""
     key = (id(scene.nodes), scene.width, scene.height)
     if getattr(ctx, "_scene_key", None) == key:
         if getattr(ctx, "_camera", None) != bytes(scene.camera):
@@ -582,8 +587,22 @@ def _bind_scene(ctx, scene) -> None:
             ctx._camera = bytes(scene.camera)
         ctx.scene = scene
         return
-    d = scene.desc()
-    check(lib().mtx_scene_upload(ctx.handle, C.byref(d)), "mtx_scene_upload")
+    token = getattr(scene, "_geom_token", None)
+    bound, prev = getattr(ctx, "_scene_key", None), ctx.scene
+    # everything a vertex update does not carry must be the bound scene's own
+    shared = ("tri_vidx", "tri_shape", "vuv", "shapes", "materials", "emitters", "textures", "texels", "tables")
+    if (token is not None and getattr(ctx, "_geom_token", None) is token and bound is not None and prev is not None
+            and bound[1:] == key[1:] and os.environ.get("MTX_REFIT_UPLOAD", "0") != "1"
+            and all(getattr(prev, a, None) is getattr(scene, a, None) for a in shared)
+            and getattr(prev, "env_radiance", None) == getattr(scene, "env_radiance", None)):
+        ctx.update_vertices(scene.vpos, scene.vnormal)  # forgets the bound scene
+        check(lib().mtx_set_camera(ctx.handle, C.byref(scene.camera)), "mtx_set_camera")
+    else:
+        d = scene.desc()
+        check(lib().mtx_scene_upload(ctx.handle, C.byref(d)), "mtx_scene_upload")
+        ctx._read_counts = {"n_nodes": int(scene.n_nodes), "n_occ_nodes": int(scene.n_occ_nodes),
+                            "n_tris": int(scene.n_tris), "n_verts": int(d.n_verts)}
+    ctx._geom_token = token
     ctx._scene_key = key
     ctx._camera = bytes(scene.camera)
     ctx._nerad_key = None  # surface tables (mtx_nerad_upload) belong to the previous scene

@@ -308,6 +308,9 @@ class Scene:
         self.tri_perm = perm  # input triangle of each leaf-order triangle
         self.n_tris = n
         self.bvh_depth = depth.value
+        # geometry base: scenes that share it (with_camera, with_vertices) have
+        # one topology, so a bound context refits instead of re-uploading
+        self._geom_token = object()
         self._build_occlusion()
 
     def _build_occlusion(self):
@@ -365,6 +368,66 @@ class Scene:
         s.camera = c2
         s.meta = dict(self.meta, width=int(c2.width), height=int(c2.height))
         return s
+
+    def with_vertices(self, vpos, vnormal=None) -> "Scene":
+        """The scene with moved vertices: assigning ``vertex_positions`` and
+        calling ``params.update()`` on ``mi.traverse(scene)``. Topology, leaf
+        order, materials and everything else are shared with this scene; the
+        new one has its own ``vpos``, ``vnormal`` (this scene's when None),
+        ``tri_geom``, ``occ_tri_geom`` and both trees' nodes, refit on the
+        host (mtx_bvh_refit, mtx_bvh_refit_occlusion) -- no rebuild. A context
+        bound to this scene takes the new one through the device refit
+        (integrators._bind_scene). Raises MtxError for a wrong vertex count, a
+        non-finite or huge coordinate, or a moved vertex of an emitter shape
+        (area emitters are analytic rectangles; they cannot be animated)."""
+        import copy
+
+        from ._lib import MtxError, check, lib
+        vpos = np.ascontiguousarray(vpos, np.float32).reshape(-1, 3)
+        if vpos.shape != self.vpos.reshape(-1, 3).shape:
+            raise MtxError(f"with_vertices: {len(vpos)} vertices given, the scene has "
+                           f"{len(self.vpos.reshape(-1, 3))} (a wrong vertex count: topology changes need a rebuild)")
+        if vnormal is None:
+            vnormal = self.vnormal
+        else:
+            vnormal = np.ascontiguousarray(vnormal, np.float32).reshape(-1, 3)
+            if vnormal.shape != vpos.shape:
+                raise MtxError(f"with_vertices: {len(vnormal)} normals for {len(vpos)} vertices")
+        vpos = vpos.reshape(self.vpos.shape)
+        vnormal = vnormal.reshape(self.vnormal.shape)
+        em_shape = np.array([sh.emitter >= 0 for sh in self.shapes], bool)
+        em_verts = np.unique(self.tri_vidx.reshape(-1, 3)[em_shape[self.tri_shape]])
+        old3, new3 = self.vpos.reshape(-1, 3), vpos.reshape(-1, 3)
+        if not np.array_equal(old3[em_verts].view(np.uint32), new3[em_verts].view(np.uint32)):
+            raise MtxError("with_vertices: a vertex of an emitter shape would move (a moved emitter vertex: area "
+                           "emitters are held analytically and cannot be animated)")
+        s = copy.copy(self)
+        s.vpos, s.vnormal = vpos.copy(), vnormal.copy()
+        s.nodes, s.occ_nodes = self.nodes.copy(), self.occ_nodes.copy()
+        s.tri_geom, s.occ_tri_geom = np.zeros_like(self.tri_geom), np.zeros_like(self.occ_tri_geom)
+        s.occ_perm = np.ascontiguousarray(self.occ_perm, np.uint32)
+        s.meta = dict(self.meta)
+        check(lib().mtx_bvh_refit(s.vpos.ctypes.data, len(new3), s.tri_vidx.ctypes.data, s.n_tris, s.nodes.ctypes.data,
+                                  s.n_nodes, s.tri_geom.ctypes.data), "mtx_bvh_refit")
+        check(lib().mtx_bvh_refit_occlusion(s.tri_geom.ctypes.data, s.occ_perm.ctypes.data, s.n_tris,
+                                            s.occ_nodes.ctypes.data, s.n_occ_nodes, s.occ_tri_geom.ctypes.data),
+              "mtx_bvh_refit_occlusion")
+        return s
+
+    def env_sphere(self) -> np.ndarray:
+        """(centre.xyz, radius) of the constant environment's bounding sphere
+        (mtx_core/interaction.h env_bsphere: the sphere of the vertices' box,
+        its radius grown by a ray epsilon), in fp32 with the header's fmas."""
+        v = self.vpos.reshape(-1, 3)
+        lo, hi = v.min(0).astype(np.float32), v.max(0).astype(np.float32)
+        eps = np.float32(1500.0) * np.float32(2.0 ** -24)
+        c = (lo + hi) * np.float32(0.5)
+        d = (c - lo).astype(np.float32)
+        acc = np.float32(d[0] * d[0])
+        for k in (1, 2):  # dot(): fma(z, z, fma(y, y, x * x)), the fma through fp64 (exact product)
+            acc = np.float32(np.float64(d[k]) * np.float64(d[k]) + np.float64(acc))
+        r = np.float32(np.sqrt(acc)) * (np.float32(1.0) + eps)
+        return np.array([c[0], c[1], c[2], max(eps, np.float32(r))], np.float32)
 
     def sensors(self) -> list:
         """scene.sensors() (testpssmlt.py:45): the scene's one sensor."""
@@ -444,6 +507,7 @@ class Scene:
          s.occ_depth) = (int(x) for x in z["counts"])
         env = z["env"] if "env" in z.files else np.zeros(4, np.float32)
         s.env_radiance = tuple(float(x) for x in env[1:]) if env[0] else None
+        s._geom_token = object()
         return s
 
 
