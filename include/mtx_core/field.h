@@ -64,9 +64,14 @@ MTX_HD uint16_t float_to_half_bits(float f) {
 
 MTX_HD float round_half(float f) { return half_bits_to_float(float_to_half_bits(f)); }
 
-// Hash-grid encoding of level l of one point (p_norm in [0,1]^3): fp16 bits
-// of the level's n_features interpolated features (f32 interpolation, one
-// rounding to fp16 per feature).
+// A level is stored dense (index x + y res + z res^2) when its res^3 vertices
+// fit the table, hashed otherwise. res^3 leaves 64 bits from res = 2^22 on
+// (level 18 of a base-16, scale-2 grid) and would wrap to a small number:
+// tables hold at most 2^26 entries, so no level above 2^9 is dense.
+MTX_HD bool field_level_dense(uint32_t res, uint32_t T) {
+  return res <= 1024u && (uint64_t)res * res * res <= (uint64_t)T;
+}
+
 // Entries (both features, packed) of corners x and x+1 of one (y, z) row.
 MTX_HD void field_fetch_pair(const uint32_t *tab, uint32_t i0, uint32_t i1, uint32_t *a, uint32_t *b) {
 #ifdef MTX_DEVICE_COMPILE
@@ -92,7 +97,7 @@ MTX_HD void field_hashgrid_level(const FieldEncoding &e, V3 pn, uint32_t l, uint
   const uint32_t T = 1u << e.log2_table;
   const float scale = e.level_scale[l];
   const uint32_t res = e.level_res[l];
-  const bool dense = (uint64_t)res * res * res <= (uint64_t)T;
+  const bool dense = field_level_dense(res, T);
   const float px = fmaf(pn.x, scale, 0.5f), py = fmaf(pn.y, scale, 0.5f), pz = fmaf(pn.z, scale, 0.5f);
   const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
   const float tx = px - fx, ty = py - fy, tz = pz - fz;
@@ -136,7 +141,7 @@ MTX_HD void field_level_corners(const FieldEncoding &e, V3 pn, uint32_t l, uint3
   const uint32_t T = 1u << e.log2_table;
   const float scale = e.level_scale[l];
   const uint32_t res = e.level_res[l];
-  const bool dense = (uint64_t)res * res * res <= (uint64_t)T;
+  const bool dense = field_level_dense(res, T);
   const float px = fmaf(pn.x, scale, 0.5f), py = fmaf(pn.y, scale, 0.5f), pz = fmaf(pn.z, scale, 0.5f);
   const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
   const float tx = px - fx, ty = py - fy, tz = pz - fz;

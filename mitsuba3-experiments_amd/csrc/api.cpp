@@ -2459,6 +2459,20 @@ static int train_check(mtx_ctx *c) {
   return MTX_OK;
 }
 
+// k_field_train keeps every layer's activation tile in LDS: a field whose
+// tiles exceed what one workgroup may hold (n_hidden >= 14 on gfx950's
+// 160 KiB) cannot be trained. Refused here, on the host, before any launch.
+static int train_fits(mtx_ctx *c) {
+  const size_t lds = mtxd::field_train_lds(c->field_hidden);
+  if (lds > c->max_lds) {
+    mtx_set_error("field training: n_hidden %u needs %zu B of LDS per workgroup, the device allows %zu B "
+                  "(inference of this field still works)",
+                  c->field_hidden, lds, c->max_lds);
+    return MTX_E_ARG;
+  }
+  return MTX_OK;
+}
+
 // Forward + backward of the field for n points (queries qp / qd on the
 // device, targets 3n floats on the device): gradients of scale * loss in
 // tr_g = [table | weights], network outputs in tr_out, loss (unscaled) on
@@ -2469,19 +2483,21 @@ static int field_backward(mtx_ctx *c, const float4 *qp, const float4 *qd, const 
   const uint32_t LF = c->field.n_levels * c->field.n_features;
   const uint32_t blocks = (n + 63) / 64;
   const uint64_t n_params = c->field_n_table + c->field_n_w;
+  if ((rc = train_fits(c))) return rc;
   if ((rc = dalloc(c->tr_feat, 128ull * n))) return rc;
   if ((rc = dalloc(c->tr_out, 12ull * n))) return rc;
   if ((rc = dalloc(c->tr_loss, 4ull * blocks))) return rc;
   if ((rc = dalloc(c->tr_wpart, 4ull * blocks * c->field_n_w))) return rc;
   if ((rc = dalloc(c->tr_dfeat, 4ull * n * LF))) return rc;
   if ((rc = dalloc(c->tr_g, 4 * n_params))) return rc;
-  mtxd::field_encode(c->field, qp, qd, nullptr, n, (uint16_t *)c->tr_feat.p, c->stream);
+  if ((rc = mtxd::field_encode(c->field, qp, qd, nullptr, n, (uint16_t *)c->tr_feat.p, c->stream))) return rc;
   HIP_TRY(hipMemsetAsync(c->tr_g.p, 0, 4 * c->field_n_table, c->stream));
   float *g = (float *)c->tr_g.p;
-  mtxd::field_train_launch((const uint16_t *)c->tr_feat.p, n, (const uint16_t *)c->field_w16.p, c->field_n_in,
-                           c->field_hidden, target, (float)(2.0 * scale / (3.0 * n)), (float *)c->tr_out.p,
-                           (float *)c->tr_loss.p, (float *)c->tr_wpart.p, g + c->field_n_table,
-                           (float *)c->tr_dfeat.p, LF, c->stream);
+  rc = mtxd::field_train_launch((const uint16_t *)c->tr_feat.p, n, (const uint16_t *)c->field_w16.p,
+                                c->field_n_in, c->field_hidden, target, (float)(2.0 * scale / (3.0 * n)),
+                                (float *)c->tr_out.p, (float *)c->tr_loss.p, (float *)c->tr_wpart.p,
+                                g + c->field_n_table, (float *)c->tr_dfeat.p, LF, c->stream);
+  if (rc) return rc;
   mtxd::field_encode_bwd_launch(c->field, qp, n, (const float *)c->tr_dfeat.p, g, c->stream);
   HIP_TRY(hipGetLastError());
   if (loss) {
@@ -2641,9 +2657,10 @@ int mtx_field_train_init(mtx_ctx *c, const mtx_field_opt *opt) {
     mtx_set_error("mtx_field_train_init: bad optimiser settings");
     return MTX_E_ARG;
   }
+  int rc;
+  if ((rc = train_fits(c))) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const uint64_t n_params = c->field_n_table + c->field_n_w;
-  int rc;
   if ((rc = dalloc(c->tr_p, 4 * n_params))) return rc;
   if ((rc = dalloc(c->tr_m, 4 * n_params))) return rc;
   if ((rc = dalloc(c->tr_v, 4 * n_params))) return rc;
@@ -2669,6 +2686,7 @@ int mtx_field_grad(mtx_ctx *c, uint64_t n, const float *p, const float *wi, cons
     mtx_set_error("mtx_field_grad: empty batch or null input");
     return MTX_E_ARG;
   }
+  if ((rc = train_fits(c))) return rc;
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = field_stage_queries(c, n, p, wi))) return rc;
   if ((rc = upload(c->tr_target, target, 3 * n, c->stream))) return rc;
@@ -2687,7 +2705,7 @@ int mtx_field_grad(mtx_ctx *c, uint64_t n, const float *p, const float *wi, cons
 int mtx_field_train_step(mtx_ctx *c, uint64_t n, const float *p, const float *wi, const float *target,
                          mtx_train_stats *stats) {
   int rc = field_check(c, n);
-  if (rc || (rc = train_check(c))) return rc;
+  if (rc || (rc = train_check(c)) || (rc = train_fits(c))) return rc;
   if (n == 0 || !p || !wi || !target) {
     mtx_set_error("mtx_field_train_step: empty batch or null input");
     return MTX_E_ARG;
@@ -2826,7 +2844,7 @@ int mtx_nerad_rhs(mtx_ctx *c, const mtx_nerad_args *a, float *L_rhs, float *lane
 
 int mtx_nerad_step(mtx_ctx *c, const mtx_nerad_args *a, mtx_train_stats *stats) {
   int rc = nerad_check(c, a);
-  if (rc || (rc = train_check(c))) return rc;
+  if (rc || (rc = train_check(c)) || (rc = train_fits(c))) return rc;
   HIP_TRY(hipSetDevice(c->device));
   PhaseTimer pt(c->stream);
   pt.mark(0);

@@ -224,7 +224,11 @@ def test_field_gradients(nscene):
 @pytest.mark.gpu
 def test_adam_and_grad_scaler(nscene):
     """One GradScaler + Adam step on fp32 master copies (drjit.opt.Adam form)
-    against numpy; a non-finite gradient skips the step and halves the scale."""
+    against numpy; a non-finite gradient skips the step and halves the scale.
+    Then, on a fresh field: three consecutive steps against a float64 Adam
+    (m, v and the bias correction for t >= 2), the scaler's growth branch
+    (growth_interval 2) and its counter reset after a backoff, and the
+    fragments re-packed on the device against the host pack."""
     from mtx.nerad import Adam, GradScaler, field_grad, field_params, field_train_init, field_train_step
 
     field = _field(nscene, seed=5, log2_table=12)
@@ -250,6 +254,8 @@ def test_adam_and_grad_scaler(nscene):
     ref = p0 - lr_t * m / (np.sqrt(vv) + 1e-8)
     np.testing.assert_allclose(np.concatenate([t1, w1]), ref, rtol=1e-5, atol=2e-7)
     np.testing.assert_allclose(m1, m, rtol=1e-3, atol=1e-12)
+    # v = 0.001 g^2 with m's tolerances carried over: m allows |dg| <= 1e-11, and d(g^2) = 2 g dg
+    assert (np.abs(v1 - vv) <= 1e-3 * vv + 0.001 * 2e-11 * np.abs(g) + 1e-25).all()
     # a NaN target -> non-finite gradients: no update, scale backs off
     bad = target.copy()
     bad[0, 0] = np.nan
@@ -257,6 +263,63 @@ def test_adam_and_grad_scaler(nscene):
     assert st["found_inf"] == 1 and st["step"] == 1 and st["scale"] == 128.0
     t2, w2, _, _ = field_params(field)
     assert np.array_equal(t2, t1) and np.array_equal(w2, w1)
+
+    # ---- three consecutive steps (bias correction for t >= 2), the scaler's
+    # growth branch, and the device re-pack of the MFMA fragments.
+    # float64 Adam with lr_t = lr sqrt(1 - b2^t) / (1 - b1^t); every step's
+    # parameters are checked from the device's previous ones, so the per-step
+    # tolerance does not have to grow with t.
+    field = _field(nscene, seed=6, log2_table=12)
+    ctx = field_train_init(field, Adam(lr=1e-3), GradScaler(init_scale=256.0, growth_interval=2))
+    flat = lambda tab, ws: np.concatenate([tab.reshape(-1), np.concatenate([x.reshape(-1) for x in ws])])
+    tk, wk, _, _ = field_params(field)
+    pk = np.concatenate([tk, wk]).astype(np.float64)
+    m, vv, scale = np.zeros_like(pk), np.zeros_like(pk), 256.0
+    for t, want_scale in ((1, 256.0), (2, 512.0), (3, 512.0)):  # the scale doubles after 2 good steps
+        _, _, gt, gw = field_grad(field, p, wi, target, scale)
+        g = flat(gt, gw).astype(np.float64) / scale
+        st = field_train_step(field, p, wi, target)
+        assert st["found_inf"] == 0 and st["step"] == t and st["scale"] == want_scale, st
+        m = 0.9 * m + 0.1 * g
+        vv = 0.999 * vv + 0.001 * g * g
+        lr_t = 1e-3 * np.sqrt(1 - 0.999 ** t) / (1 - 0.9 ** t)
+        tk, wk, mk, vk = field_params(field)
+        got = np.concatenate([tk, wk])
+        np.testing.assert_allclose(got, pk - lr_t * m / (np.sqrt(vv) + 1e-8), rtol=1e-5, atol=2e-7)
+        np.testing.assert_allclose(mk, m, rtol=1e-3, atol=1e-12)
+        assert (np.abs(vk - vv) <= 1e-3 * vv + 0.001 * 2e-11 * np.abs(g) * t + 1e-25).all()
+        pk, scale = got.astype(np.float64), st["scale"]
+    st = field_train_step(field, p, wi, bad)
+    assert st["found_inf"] == 1 and st["step"] == 3 and st["scale"] == 256.0
+    # the backoff reset the counter: two more good steps before the scale doubles again
+    st = field_train_step(field, p, wi, target)
+    assert st["found_inf"] == 0 and st["step"] == 4 and st["scale"] == 256.0
+    st = field_train_step(field, p, wi, target)
+    assert st["found_inf"] == 0 and st["step"] == 5 and st["scale"] == 512.0
+    _assert_repack_matches_host(field, p, wi, ctx)
+
+
+def _assert_repack_matches_host(field, p, wi, ctx):
+    """The field a trained context evaluates runs on the MFMA fragments that
+    k_field_prepack_dev wrote after the last step. A new Field with the fp16
+    casts of the fp32 master parameters, uploaded to the same context, goes
+    through the host field_prepack: the two must agree bit for bit."""
+    from mtx.field import Field
+    from mtx.nerad import field_params
+
+    live = field(p, wi, ctx=ctx)
+    t32, w32, _, _ = field_params(field, ctx=ctx)
+    f2 = Field(bbox=(field.bbox_min, field.bbox_max), n_hidden=field.n_hidden, n_levels=field.n_levels,
+               n_features=field.n_features, log2_table=field.log2_table, base_res=field.base_res,
+               per_level_scale=field.per_level_scale)
+    f2.table = t32.astype(np.float16).reshape(field.table.shape)
+    ws, o = [], 0
+    for x in field.weights:
+        ws.append(w32[o:o + x.size].astype(np.float16).reshape(x.shape))
+        o += x.size
+    f2.weights = ws
+    assert np.array_equal(f2(p, wi, ctx=ctx), live)
+    assert np.abs(live).max() > 0
 
 
 @pytest.mark.gpu
@@ -297,6 +360,7 @@ def test_training_reduces_loss(nscene):
     assert np.array_equal(field.weights[0], ws[0].astype(np.float16))
     feat = field.features(p, wi, ctx=tr.ctx)
     np.testing.assert_allclose(live, field.mlp_reference(feat), atol=2e-2 * max(1.0, np.abs(live).max()))
+    _assert_repack_matches_host(field, p, wi, tr.ctx)
 
 
 @pytest.mark.gpu
