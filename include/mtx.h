@@ -78,13 +78,49 @@ typedef struct mtx_texture {
   uint64_t offset; /* offset (in floats) into texels[], RGB interleaved, linear */
 } mtx_texture;
 
-/* Area emitter on a `rectangle` shape (scene.xml:706-731). */
+/* Area emitter on a shape: an analytic `rectangle` (scene.xml:706-731) or a
+ * triangle mesh (`obj`, `cube`). Both forms share the 64-B record; the first
+ * nine words are a union.
+ *
+ * Rectangle: center / col0 / col1 describe the affine unit square, `normal`
+ * is unit length.
+ *
+ * Mesh: `normal` is (0, 0, 0) -- that is what marks the record -- and the
+ * union holds the discrete distribution over the shape's triangles (Mitsuba's
+ * DiscreteDistribution, mtx_core/discrete.h), whose arrays lie in the scene's
+ * float `tables` from `mesh_offset` on (after the roughplastic tables):
+ *   pmf[mesh_count]   fp32 triangle areas
+ *   cdf[mesh_count]   inclusive prefix, accumulated in double, stored as float
+ *   prim[mesh_count]  scene (closest-hit leaf-order) triangle of each entry,
+ *                     uint32 bit patterns
+ * mesh_valid_lo / _hi are the first / last entry with a non-zero pmf,
+ * mesh_sum = cdf[mesh_count - 1], mesh_norm = 1 / mesh_sum, mesh_kind =
+ * MTX_EMITTER_MESH, inv_area = 1 / (sum of the triangle areas). The shape
+ * that carries a mesh emitter is shaded with face normals (flag bit 0).
+ * mtx_scene_upload refuses (MTX_E_ARG) a mesh record whose table range leaves
+ * `tables`, whose entries are not exactly the triangles of the shapes that
+ * name the emitter, whose cdf decreases, or whose sum is not positive. */
+#define MTX_EMITTER_MESH 1u
 typedef struct mtx_emitter {
-  float center[3];  /* to_world translation */
-  float col0[3];    /* to_world * (1,0,0) */
-  float col1[3];    /* to_world * (0,1,0) */
-  float normal[3];  /* normalize(inverse-transpose(to_world) * (0,0,1)) */
-  float inv_area;   /* 1 / |cross(2 col0, 2 col1)| */
+  union {
+    struct {
+      float center[3];  /* to_world translation */
+      float col0[3];    /* to_world * (1,0,0) */
+      float col1[3];    /* to_world * (0,1,0) */
+    };
+    struct {
+      uint32_t mesh_offset;   /* first float of pmf | cdf | prim in tables[] */
+      uint32_t mesh_count;    /* entries (triangles) */
+      uint32_t mesh_valid_lo; /* first entry with pmf > 0 */
+      uint32_t mesh_valid_hi; /* last entry with pmf > 0 */
+      float mesh_sum;         /* cdf[mesh_count - 1] */
+      float mesh_norm;        /* 1 / mesh_sum */
+      uint32_t mesh_kind;     /* MTX_EMITTER_MESH */
+      uint32_t mesh_pad[2];   /* 0 */
+    };
+  };
+  float normal[3];  /* rectangle: normalize(inverse-transpose(to_world) * (0,0,1)); mesh: 0 */
+  float inv_area;   /* rectangle: 1 / |cross(2 col0, 2 col1)|; mesh: 1 / total triangle area */
   float radiance[3];
 } mtx_emitter;
 
@@ -178,7 +214,7 @@ typedef struct mtx_scene_desc {
   const mtx_texture *textures;
   const float *texels;
   uint64_t n_texels;         /* floats */
-  const float *tables;       /* roughplastic transmittance tables */
+  const float *tables;       /* roughplastic transmittance tables, then mesh emitters' pmf | cdf | prim */
   uint32_t n_tables;         /* floats */
   uint32_t pad0;
   mtx_camera camera;

@@ -1,15 +1,17 @@
 // mtx_core/interaction.h — surface interactions, ray spawning, the rectangle
-// area emitter, the constant environment emitter, the perspective sensor and
-// the two MIS weight variants.
+// and triangle-mesh area emitters, the constant environment emitter, the
+// perspective sensor and the two MIS weight variants.
 // Upstream semantics restated (unverifiable offline):
 //   Mesh::compute_surface_interaction, Interaction::spawn_ray(_to),
 //   Scene::sample_emitter_direction / pdf_emitter_direction,
-//   AreaEmitter + Rectangle, ConstantBackgroundEmitter (`constant`),
+//   AreaEmitter + Rectangle, AreaEmitter + Mesh (Mesh::sample_position),
+//   ConstantBackgroundEmitter (`constant`),
 //   PerspectiveCamera::sample_ray.
 #pragma once
 #include "../mtx.h"
 #include "bsdf.h"
 #include "common.h"
+#include "discrete.h"
 #include "warp.h"
 
 namespace mtx {
@@ -131,14 +133,27 @@ MTX_HD SurfaceInteraction si_from_vertices(float t, uint32_t prim, float u, floa
   return si;
 }
 
+// The vertices of leaf-order triangle `prim` (tri_vidx -> vpos), read the
+// same way by compute_si and by the mesh emitter's position sample.
+MTX_HD void tri_vertices(const SceneView &s, uint32_t prim, uint32_t idx[3], V3 *p0, V3 *p1, V3 *p2) {
+  idx[0] = s.tri_vidx[3 * (size_t)prim + 0];
+  idx[1] = s.tri_vidx[3 * (size_t)prim + 1];
+  idx[2] = s.tri_vidx[3 * (size_t)prim + 2];
+  *p0 = load3(s.vpos, idx[0]);
+  *p1 = load3(s.vpos, idx[1]);
+  *p2 = load3(s.vpos, idx[2]);
+}
+
 MTX_HD SurfaceInteraction compute_si(const SceneView &s, float t, uint32_t prim, float u, float v, V3 ray_d) {
   if (prim == 0xffffffffu) {  // a miss: si.emitter(scene) is the environment, if any
     SurfaceInteraction si = si_invalid(t, prim, ray_d);
     si.emitter = env_index(s);
     return si;
   }
-  const uint32_t i0 = s.tri_vidx[3 * prim + 0], i1 = s.tri_vidx[3 * prim + 1], i2 = s.tri_vidx[3 * prim + 2];
-  const V3 p0 = load3(s.vpos, i0), p1 = load3(s.vpos, i1), p2 = load3(s.vpos, i2);
+  uint32_t vi[3];
+  V3 p0, p1, p2;
+  tri_vertices(s, prim, vi, &p0, &p1, &p2);
+  const uint32_t i0 = vi[0], i1 = vi[1], i2 = vi[2];
   const mtx_shape sh = s.shapes[s.tri_shape[prim]];
   const bool use_n = !(sh.flags & 1u) && s.vnormal;
   const bool use_uv = (sh.flags & 2u) && s.vuv;
@@ -185,9 +200,71 @@ struct DirectionSample {
   int32_t emitter;
 };
 
+// A mesh area emitter's record (mtx.h: a zero normal; a rectangle's is unit
+// length) as the distribution over its triangles, whose arrays lie in the
+// scene's float tables: pmf[n], cdf[n], then the leaf-order triangle of each
+// entry as a bit pattern. mtx_scene_upload has checked the range, the
+// triangle indices and the cdf before a kernel reads any of them.
+MTX_HD bool emitter_is_mesh(const mtx_emitter &e) { return all_zero(V3{e.normal[0], e.normal[1], e.normal[2]}); }
+MTX_HD DiscreteDist mesh_emitter_dist(const mtx_emitter &e, const float *tables) {
+  DiscreteDist d;
+  d.n = e.mesh_count;
+  d.pmf = tables + e.mesh_offset;
+  d.cdf = d.pmf + d.n;
+  d.valid_lo = e.mesh_valid_lo;
+  d.valid_hi = e.mesh_valid_hi;
+  d.sum = e.mesh_sum;
+  d.normalization = e.mesh_norm;
+  return d;
+}
+
+// Mesh::sample_position: a triangle by area with the reused sample.y
+// (DiscreteDistribution::sample_reuse), warp::square_to_uniform_triangle,
+// p = fma(e1, b.x, fma(e2, b.y, p0)); the normal is the face normal of
+// si_from_vertices (an emitting mesh is shaded with face normals, so the hit
+// side's pdf_emitter_direction sees the same normal).
+MTX_HD void mesh_emitter_sample_position(const SceneView &s, const mtx_emitter &e, V2 u, V3 *p, V3 *n) {
+  const DiscreteDist d = mesh_emitter_dist(e, s.bsdf.tables);
+  float y2;
+  uint32_t k, prim;
+#if defined(__HIP_DEVICE_COMPILE__)
+  // The lanes of a wave usually search one distribution (a scene with one
+  // mesh light; neighbouring pixels that picked the same emitter). Then the
+  // record's words are wave-uniform: taken from the first active lane they
+  // stay in SGPRs, so the table base is a scalar address, the trip count a
+  // scalar loop bound, and the lanes differ in the cdf index alone. Same
+  // values, same search, same result as the per-lane form below.
+  const uint32_t off0 = __builtin_amdgcn_readfirstlane(e.mesh_offset);
+  if (__builtin_amdgcn_ballot_w64(e.mesh_offset != off0) == 0) {
+    DiscreteDist w;
+    w.n = __builtin_amdgcn_readfirstlane(d.n);
+    w.pmf = s.bsdf.tables + off0;
+    w.cdf = w.pmf + w.n;
+    w.valid_lo = __builtin_amdgcn_readfirstlane(d.valid_lo);
+    w.valid_hi = __builtin_amdgcn_readfirstlane(d.valid_hi);
+    w.sum = u2f(__builtin_amdgcn_readfirstlane(f2u(d.sum)));
+    w.normalization = u2f(__builtin_amdgcn_readfirstlane(f2u(d.normalization)));
+    k = discrete_sample_reuse_fixed(w, u.y, &y2);
+    prim = f2u(w.cdf[w.n + k]);
+  } else
+#endif
+  {
+    k = discrete_sample_reuse_fixed(d, u.y, &y2);
+    prim = f2u(d.cdf[d.n + k]);
+  }
+  u.y = y2;
+  const V2 b = square_to_uniform_triangle(u);
+  uint32_t vi[3];
+  V3 p0, p1, p2;
+  tri_vertices(s, prim, vi, &p0, &p1, &p2);
+  const V3 e1 = p1 - p0, e2 = p2 - p0;
+  *p = fma3(e1, b.x, fma3(e2, b.y, p0));
+  *n = normalize(cross(e1, e2));
+}
+
 // Scene::sample_emitter_direction(ref, sample, test_visibility) without the
 // visibility test (the caller traces the shadow ray): uniform emitter pick,
-// Rectangle::sample_position, Shape::sample_direction (area -> solid angle),
+// Rectangle:: / Mesh::sample_position, Shape::sample_direction (area -> solid angle),
 // AreaEmitter::sample_direction (one-sided). Returns the emitter weight
 // (radiance / pdf, times the emitter count); `ds.pdf` includes the pick pdf.
 MTX_HD V3 sample_emitter_direction(const SceneView &s, V3 ref_p, V2 u, DirectionSample *ds) {
@@ -218,13 +295,19 @@ MTX_HD V3 sample_emitter_direction(const SceneView &s, V3 ref_p, V2 u, Direction
     return spec;
   }
   const mtx_emitter e = s.emitters[index];
-  // Rectangle::sample_position: to_world.transform_affine((2u-1, 2v-1, 0))
-  float lx = fmaf(u.x, 2.f, -1.f), ly = fmaf(u.y, 2.f, -1.f);
-  V3 c0 = V3{e.col0[0], e.col0[1], e.col0[2]}, c1 = V3{e.col1[0], e.col1[1], e.col1[2]};
-  V3 ctr = V3{e.center[0], e.center[1], e.center[2]};
-  V3 p = fma3(c0, lx, fma3(c1, ly, ctr));
+  V3 p, n;
+  if (emitter_is_mesh(e)) {
+    mesh_emitter_sample_position(s, e, u, &p, &n);
+  } else {
+    // Rectangle::sample_position: to_world.transform_affine((2u-1, 2v-1, 0))
+    float lx = fmaf(u.x, 2.f, -1.f), ly = fmaf(u.y, 2.f, -1.f);
+    V3 c0 = V3{e.col0[0], e.col0[1], e.col0[2]}, c1 = V3{e.col1[0], e.col1[1], e.col1[2]};
+    V3 ctr = V3{e.center[0], e.center[1], e.center[2]};
+    p = fma3(c0, lx, fma3(c1, ly, ctr));
+    n = V3{e.normal[0], e.normal[1], e.normal[2]};
+  }
   ds->p = p;
-  ds->n = V3{e.normal[0], e.normal[1], e.normal[2]};
+  ds->n = n;
   ds->emitter = (int32_t)index;
   // Shape::sample_direction
   V3 d = p - ref_p;

@@ -6,8 +6,8 @@
 //     then shape.sample_position(0, u2) and a uniform sphere / hemisphere
 //     direction for two-sided / one-sided BSDFs (:297-308).
 //   Upstream pieces restated (Mitsuba 3 core, unverifiable offline; parity
-//   unpinned): DiscreteDistribution::sample / sample_reuse (cdf accumulated
-//   in double, stored as float; search restricted to the non-zero range),
+//   unpinned): DiscreteDistribution::sample / sample_reuse (discrete.h: cdf
+//   accumulated in double, stored as float; search restricted to the non-zero range),
 //   Mesh::sample_position (triangle by area with the reused sample.y, then
 //   warp::square_to_uniform_triangle), warp::square_to_uniform_sphere.
 //   Restatement choices: a mesh's triangles are in BVH leaf order (the OBJ
@@ -17,49 +17,11 @@
 //   frame come from the same code as a ray hit.
 #pragma once
 #include "common.h"
+#include "discrete.h"
 #include "rng.h"
 #include "warp.h"
 
 namespace mtx {
-
-// One DiscreteDistribution: pmf[n], cdf[n] (inclusive prefix, double-
-// accumulated, stored as float), sum = cdf[n-1], normalization = 1/sum, and
-// the first / last index with a non-zero pmf (upstream m_valid).
-struct DiscreteDist {
-  const float *pmf, *cdf;
-  uint32_t n, valid_lo, valid_hi;
-  float sum, normalization;
-};
-
-// DiscreteDistribution::sample: the first index in [valid_lo, valid_hi]
-// whose cdf is not below u * sum.
-MTX_HD uint32_t discrete_sample(const DiscreteDist &d, float u) {
-  const float value = u * d.sum;
-  uint32_t lo = d.valid_lo, hi = d.valid_hi;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (d.cdf[mid] < value)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
-// DiscreteDistribution::sample_reuse: index and the sample rescaled to
-// [0, 1) inside the chosen interval.
-MTX_HD uint32_t discrete_sample_reuse(const DiscreteDist &d, float u, float *u_out) {
-  const uint32_t i = discrete_sample(d, u);
-  const float pmf = d.pmf[i] * d.normalization;
-  const float cdf = i > 0 ? d.cdf[i - 1] * d.normalization : 0.f;
-  *u_out = (u - cdf) / pmf;
-  return i;
-}
-
-MTX_HD V2 square_to_uniform_triangle(V2 s) {
-  const float t = safe_sqrt(1.f - s.x);
-  return V2{1.f - t, t * s.y};
-}
 
 // Surface-area tables of a scene (built on the host, mtx/nerad.py): the
 // shape distribution and, per shape, the distribution over its triangles

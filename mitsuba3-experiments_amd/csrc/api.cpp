@@ -395,6 +395,86 @@ static int upload_levels(const std::vector<uint32_t> &level, uint32_t depth, std
   return MTX_OK;
 }
 
+// Mesh area emitters (mtx.h mtx_emitter: a zero normal): the kernels index
+// `tables` and the triangles from the record's words, so every word is
+// checked here, on the host, before anything reaches the device. Called once
+// tri_shape and the shapes' emitter references are known to be in range.
+static int check_mesh_emitters(const mtx_scene_desc *d) {
+  std::vector<uint32_t> listed;  // per triangle: times a mesh record lists it
+  for (uint32_t i = 0; i < d->n_emitters; ++i) {
+    const mtx_emitter &e = d->emitters[i];
+    if (!(e.normal[0] == 0.f && e.normal[1] == 0.f && e.normal[2] == 0.f)) continue;  // a rectangle
+    const uint64_t n = e.mesh_count;
+    if (e.mesh_kind != MTX_EMITTER_MESH || n == 0) {
+      mtx_set_error("mtx_scene_upload: emitter %u has a zero normal but is no mesh record (kind %u, %u entries)", i,
+                    e.mesh_kind, e.mesh_count);
+      return MTX_E_ARG;
+    }
+    if (!d->tables || (uint64_t)e.mesh_offset + 3 * n > d->n_tables) {
+      mtx_set_error("mtx_scene_upload: mesh emitter %u: table range [%u, +3 x %u) leaves the %u table floats", i,
+                    e.mesh_offset, e.mesh_count, d->n_tables);
+      return MTX_E_ARG;
+    }
+    const float *pmf = d->tables + e.mesh_offset, *cdf = pmf + n;
+    if (!(e.mesh_sum > 0.f) || !std::isfinite(e.mesh_sum) || e.mesh_sum != cdf[n - 1] || !(e.mesh_norm > 0.f) ||
+        !std::isfinite(e.mesh_norm) || !(e.inv_area > 0.f) || !std::isfinite(e.inv_area)) {
+      mtx_set_error("mtx_scene_upload: mesh emitter %u: sum %g (cdf ends at %g), normalization %g, inv_area %g: "
+                    "need a positive finite sum equal to the last cdf entry", i, (double)e.mesh_sum,
+                    (double)cdf[n - 1], (double)e.mesh_norm, (double)e.inv_area);
+      return MTX_E_ARG;
+    }
+    uint32_t lo = 0xffffffffu, hi = 0;
+    for (uint64_t k = 0; k < n; ++k) {
+      if (!(pmf[k] >= 0.f) || !(cdf[k] >= (k ? cdf[k - 1] : 0.f))) {
+        mtx_set_error("mtx_scene_upload: mesh emitter %u: entry %llu has a negative pmf or a decreasing cdf", i,
+                      (unsigned long long)k);
+        return MTX_E_ARG;
+      }
+      if (pmf[k] > 0.f) {
+        if (lo == 0xffffffffu) lo = (uint32_t)k;
+        hi = (uint32_t)k;
+      }
+    }
+    if (lo != e.mesh_valid_lo || hi != e.mesh_valid_hi) {
+      mtx_set_error("mtx_scene_upload: mesh emitter %u: valid range [%u, %u] given, the pmf's is [%u, %u]", i,
+                    e.mesh_valid_lo, e.mesh_valid_hi, lo, hi);
+      return MTX_E_ARG;
+    }
+    if (listed.empty()) listed.assign(d->n_tris, 0u);
+    for (uint64_t k = 0; k < n; ++k) {
+      uint32_t prim;
+      memcpy(&prim, cdf + n + k, 4);
+      if (prim >= d->n_tris) {
+        mtx_set_error("mtx_scene_upload: mesh emitter %u: entry %llu names triangle %u of %u", i,
+                      (unsigned long long)k, prim, d->n_tris);
+        return MTX_E_ARG;
+      }
+      if (d->shapes[d->tri_shape[prim]].emitter != (int32_t)i || listed[prim]++) {
+        mtx_set_error("mtx_scene_upload: mesh emitter %u: entry %llu names triangle %u, which %s", i,
+                      (unsigned long long)k, prim,
+                      listed[prim] > 1 ? "is listed twice" : "belongs to a shape with another emitter or none");
+        return MTX_E_ARG;
+      }
+    }
+  }
+  for (uint32_t t = 0; t < d->n_tris; ++t) {
+    const mtx_shape &sh = d->shapes[d->tri_shape[t]];
+    if (sh.emitter < 0) continue;
+    const mtx_emitter &e = d->emitters[sh.emitter];
+    if (!(e.normal[0] == 0.f && e.normal[1] == 0.f && e.normal[2] == 0.f)) continue;
+    if (listed.empty() || listed[t] != 1) {
+      mtx_set_error("mtx_scene_upload: mesh emitter %d does not list triangle %u of its shape", sh.emitter, t);
+      return MTX_E_ARG;
+    }
+    if (!(sh.flags & 1u)) {
+      mtx_set_error("mtx_scene_upload: shape %u carries mesh emitter %d and must be shaded with face normals "
+                    "(flag bit 0)", d->tri_shape[t], sh.emitter);
+      return MTX_E_ARG;
+    }
+  }
+  return MTX_OK;
+}
+
 int mtx_scene_upload(mtx_ctx *c, const mtx_scene_desc *d) {
   if (!c || !d) {
     mtx_set_error("mtx_scene_upload: null argument");
@@ -525,6 +605,7 @@ int mtx_scene_upload(mtx_ctx *c, const mtx_scene_desc *d) {
       return MTX_E_ARG;
     }
   }
+  if ((rc = check_mesh_emitters(d))) return rc;
   for (uint32_t i = 0; i < d->n_materials; ++i) {
     const mtx_material &m = d->materials[i];
     if (m.tex >= 0) {
@@ -1746,8 +1827,9 @@ int mtx_scene_update_vertices(mtx_ctx *c, const float *vpos, const float *vnorma
     return MTX_E_ARG;
   }
   if (h[mtxd::RF_FLAGS] & mtxd::RF_BAD_EMITTER) {
-    mtx_set_error("mtx_scene_update_vertices: a vertex of an emitter shape would move (area emitters are held "
-                  "analytically and cannot be animated); the scene is unchanged");
+    mtx_set_error("mtx_scene_update_vertices: a vertex of an emitter shape would move (a rectangle emitter is "
+                  "held analytically and a mesh emitter's triangle distribution is built at load time; neither can "
+                  "be animated); the scene is unchanged");
     return MTX_E_ARG;
   }
   // from here on the scene is written

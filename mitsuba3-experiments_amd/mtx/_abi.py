@@ -76,7 +76,14 @@ class Texture(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("offset", C.c_uint64)]
 
 
+MTX_EMITTER_MESH = 1
+
+
 class Emitter(C.Structure):
+    """mtx_emitter. The fields are the rectangle's; a mesh emitter (a zero
+    ``normal``) overlays the first nine words with its triangle distribution
+    (mtx.h), read and written here through ``mesh`` / ``set_mesh`` as bit
+    patterns."""
     _fields_ = [
         ("center", C.c_float * 3),
         ("col0", C.c_float * 3),
@@ -85,6 +92,34 @@ class Emitter(C.Structure):
         ("inv_area", C.c_float),
         ("radiance", C.c_float * 3),
     ]
+    _MESH_WORDS = ("offset", "count", "valid_lo", "valid_hi", "sum", "norm", "kind")
+
+    @property
+    def is_mesh(self) -> bool:
+        return tuple(self.normal) == (0.0, 0.0, 0.0)
+
+    def _words(self):
+        return (C.c_uint32 * 16).from_buffer(self)
+
+    @property
+    def mesh(self) -> dict:
+        """The mesh overlay's words: offset, count, valid_lo, valid_hi (uint32),
+        sum, norm (float), kind."""
+        import struct
+        w = self._words()
+        out = {k: int(w[i]) for i, k in enumerate(self._MESH_WORDS)}
+        for i, k in ((4, "sum"), (5, "norm")):
+            out[k] = struct.unpack("<f", struct.pack("<I", w[i]))[0]
+        return out
+
+    def set_mesh(self, offset: int, count: int, valid_lo: int, valid_hi: int, sum: float, norm: float):
+        import struct
+        w = self._words()
+        w[0], w[1], w[2], w[3] = int(offset), int(count), int(valid_lo), int(valid_hi)
+        w[4] = struct.unpack("<I", struct.pack("<f", float(sum)))[0]
+        w[5] = struct.unpack("<I", struct.pack("<f", float(norm)))[0]
+        w[6], w[7], w[8] = MTX_EMITTER_MESH, 0, 0
+        self.normal[:] = (0.0, 0.0, 0.0)
 
 
 class Shape(C.Structure):

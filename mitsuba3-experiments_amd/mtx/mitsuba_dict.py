@@ -18,9 +18,12 @@ fov_axis x / y / smaller / larger, near / far clip, ``hdrfilm`` size) with
 a ``to_world`` transform; BSDFs diffuse, roughplastic, conductor,
 roughconductor, dielectric, roughdielectric, twosided, mask, with rgb /
 scalar / bitmap values and ``ref`` references; shapes rectangle, cube and
-obj (``filename``, read from ``base_dir``), with an ``area`` emitter on
-rectangles; a ``constant`` environment emitter (``radiance`` rgb or float;
-mtx_core/interaction.h). Anything else -- including an ``obj`` whose file is
+obj (``filename``, read from ``base_dir``), any of them with an ``area``
+emitter (a rectangle's is held analytically; an emitting cube or obj is a
+mesh emitter, sampled by triangle area and shaded with face normals -- its
+vertex normals are ignored, where Mitsuba interpolates them); a ``constant``
+environment emitter (``radiance`` rgb or float; mtx_core/interaction.h).
+Anything else -- point, spot and directional lights, an ``obj`` whose file is
 missing and ``envmap`` environments (see ENV_EMITTERS) -- raises
 :class:`mtx.MtxError` rather than rendering a different scene.
 """
@@ -143,8 +146,8 @@ def spec_from_dict(d: dict) -> dict:
             if t == "obj" and not v.get("filename"):
                 raise MtxError(f"shape {key!r}: an obj shape needs a filename")
             if em is not None:
-                if em.get("type") != "area" or t != "rectangle":
-                    raise MtxError(f"shape {key!r}: only area emitters on rectangles are supported")
+                if not isinstance(em, dict) or em.get("type") != "area":
+                    raise MtxError(f"shape {key!r}: only area emitters are supported on shapes")
                 sd["emitter"] = {"type": "area", "radiance": _value(em.get("radiance", [1.0, 1.0, 1.0]))}
             shapes.append(sd)
         elif t in _IGNORED or key in _IGNORED:
@@ -155,10 +158,11 @@ def spec_from_dict(d: dict) -> dict:
             env = {"type": "constant", "radiance": _value(v.get("radiance", 1.0))}
         elif t in ENV_EMITTERS:
             raise MtxError(f"scene entry {key!r}: environment emitter {t!r} is not supported -- mtx evaluates "
-                           "rectangle area emitters and a constant environment only "
+                           "area emitters (rectangles and meshes) and a constant environment only "
                            "(path-mis.py:41 / :84 would read the envmap where a ray escapes)")
         elif t in OTHER_EMITTERS:
-            raise MtxError(f"scene entry {key!r}: {t!r} emitters are not supported (rectangle area emitters only)")
+            raise MtxError(f"scene entry {key!r}: {t!r} emitters are not supported (area emitters on shapes and a "
+                           "constant environment only)")
         else:
             raise MtxError(f"scene entry {key!r}: unsupported type {t!r}")
     if sensor is None:

@@ -170,6 +170,7 @@ class Scene:
         # ---------------- shapes
         P_all, N_all, UV_all, F_all, shape_of_tri = [], [], [], [], []
         shapes, emitters = [], []
+        mesh_emitters, mesh_normals_dropped = [], []
         nv = 0
         family_count = {}
         budgets = {}
@@ -232,7 +233,24 @@ class Scene:
                 mid = len(mats)
                 mats.append(convert(sd["bsdf_inline"]))
             em = -1
-            if "emitter" in sd:
+            if "emitter" in sd and sd["emitter"].get("type", "area") != "area":
+                from ._lib import MtxError
+                raise MtxError(f"shape {sd['id']!r}: only area emitters are supported on shapes, not "
+                               f"{sd['emitter'].get('type')!r}")
+            if "emitter" in sd and sd["type"] != "rectangle":
+                # a mesh area emitter: the record is completed from the
+                # leaf-order triangles once the BVH is built
+                # (_build_mesh_emitters). Sampling and the hit side's pdf must
+                # see one normal, so the shape is shaded with face normals.
+                em = len(emitters)
+                if not (flags & 1):
+                    mesh_normals_dropped.append(sd["id"])
+                flags |= 1
+                e = _abi.Emitter()
+                e.radiance[:] = sd["emitter"]["radiance"]
+                emitters.append(e)
+                mesh_emitters.append(em)
+            elif "emitter" in sd:
                 em = len(emitters)
                 e = _abi.Emitter()
                 e.center[:] = M[:3, 3]
@@ -270,6 +288,11 @@ class Scene:
         env = spec.get("environment")
         s.env_radiance = None if env is None else tuple(float(x) for x in _rgb3(env["radiance"]))
         s._build_bvh(tri_vidx, tri_shape)
+        s._build_mesh_emitters(mesh_emitters)
+        if mesh_normals_dropped:
+            import warnings
+            warnings.warn("mtx: emitting meshes are shaded with face normals; the vertex normals of "
+                          f"{', '.join(mesh_normals_dropped)} are ignored (Mitsuba interpolates them)", stacklevel=2)
         s.rfilter = str(film.get("rfilter") or "tent")
         s.meta = {"scene": "bedroom-proxy" if not loaded else "xml", "proxy_version": proxy.PROXY_VERSION,
                   "fov_axis": spec["sensor"].get("fov_axis", "x"), "rfilter": s.rfilter,
@@ -288,6 +311,39 @@ class Scene:
         spec = parse_scene_xml(path)
         return cls.bedroom(width, height, scale=scale, tex_res=tex_res, spec=spec,
                            base_dir=os.path.dirname(os.path.abspath(path)))
+
+    def _build_mesh_emitters(self, mesh_emitters):
+        """Complete the records of mesh area emitters (mtx.h mtx_emitter): per
+        emitter the DiscreteDistribution over its shape's triangles in leaf
+        order -- pmf the fp32 triangle area (Mesh::face_area: half the norm of
+        the edge cross product, in the header's fp32 arithmetic), cdf the
+        inclusive prefix accumulated in double and stored as float -- and the
+        triangle of each entry, appended to ``tables``. No triangle is
+        skipped: a zero-area one has pmf 0 and is never chosen."""
+        if not mesh_emitters:
+            return
+        from ._lib import MtxError
+        shape_em = np.array([sh.emitter for sh in self.shapes], np.int64)
+        tri_em = shape_em[self.tri_shape]
+        vid = self.tri_vidx.reshape(-1, 3)
+        v = self.vpos.reshape(-1, 3)
+        blocks, off = [self.tables[: self.n_tables]], self.n_tables
+        for em in mesh_emitters:
+            prims = np.flatnonzero(tri_em == em).astype(np.uint32)
+            p0, p1, p2 = (v[vid[prims, k]] for k in range(3))
+            pmf = _tri_area_f32(p0, p1, p2)
+            cdf = np.cumsum(pmf.astype(np.float64)).astype(np.float32)
+            nz = np.flatnonzero(pmf > 0)
+            if len(nz) == 0 or not np.isfinite(cdf[-1]):
+                raise MtxError(f"mesh emitter {em}: its {len(prims)} triangles have no finite positive area")
+            total = np.float32(cdf[-1])
+            e = self.emitters[em]
+            e.set_mesh(off, len(prims), nz[0], nz[-1], total, np.float32(1.0) / total)
+            e.inv_area = np.float32(1.0) / total
+            blocks += [pmf, cdf, prims.view(np.float32)]
+            off += 3 * len(prims)
+        self.tables = np.ascontiguousarray(np.concatenate(blocks).astype(np.float32, copy=False))
+        self.n_tables = int(off)
 
     def _build_bvh(self, tri_vidx, tri_shape):
         from ._lib import check, lib
@@ -379,7 +435,8 @@ class Scene:
         bound to this scene takes the new one through the device refit
         (integrators._bind_scene). Raises MtxError for a wrong vertex count, a
         non-finite or huge coordinate, or a moved vertex of an emitter shape
-        (area emitters are analytic rectangles; they cannot be animated)."""
+        (rectangle emitters are analytic and a mesh emitter's triangle tables
+        are built at load time; neither can be animated)."""
         import copy
 
         from ._lib import MtxError, check, lib
@@ -399,8 +456,10 @@ class Scene:
         em_verts = np.unique(self.tri_vidx.reshape(-1, 3)[em_shape[self.tri_shape]])
         old3, new3 = self.vpos.reshape(-1, 3), vpos.reshape(-1, 3)
         if not np.array_equal(old3[em_verts].view(np.uint32), new3[em_verts].view(np.uint32)):
-            raise MtxError("with_vertices: a vertex of an emitter shape would move (a moved emitter vertex: area "
-                           "emitters are held analytically and cannot be animated)")
+            raise MtxError("with_vertices: a vertex of an emitter shape would move (a moved emitter vertex: a "
+                           "rectangle emitter is held analytically and a mesh emitter's triangle distribution is "
+                           "built at load time, so a moved mesh light would need its tables rebuilt; neither can be "
+                           "animated)")
         s = copy.copy(self)
         s.vpos, s.vnormal = vpos.copy(), vnormal.copy()
         s.nodes, s.occ_nodes = self.nodes.copy(), self.occ_nodes.copy()
@@ -522,6 +581,25 @@ class Sensor:
 
     def film_size(self) -> tuple:
         return int(self.camera.width), int(self.camera.height)
+
+
+def _tri_area_f32(p0, p1, p2):
+    """fp32 triangle areas, 0.5 * norm(cross(p1 - p0, p2 - p0)) with the
+    rounding of mtx_core/common.h (cross: fma(a, b, -(c * d)); dot:
+    fma(z, z, fma(y, y, x * x)); the fmas through exact fp64 products)."""
+    f32, f64 = np.float32, np.float64
+    a = (p1 - p0).astype(f32)
+    b = (p2 - p0).astype(f32)
+
+    def fmsub(x, y, z, w):  # fma(x, y, -(z * w))
+        return (x.astype(f64) * y.astype(f64) - (z * w).astype(f32).astype(f64)).astype(f32)
+    cx = fmsub(a[:, 1], b[:, 2], a[:, 2], b[:, 1])
+    cy = fmsub(a[:, 2], b[:, 0], a[:, 0], b[:, 2])
+    cz = fmsub(a[:, 0], b[:, 1], a[:, 1], b[:, 0])
+    acc = (cx * cx).astype(f32)
+    for c in (cy, cz):
+        acc = (c.astype(f64) * c.astype(f64) + acc.astype(f64)).astype(f32)
+    return (np.sqrt(acc).astype(f32) * f32(0.5)).astype(f32)
 
 
 def _cube_mesh():

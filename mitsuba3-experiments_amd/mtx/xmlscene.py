@@ -4,8 +4,8 @@ Covers what ``data/bedroom/scene.xml`` uses: ``<default>``
 and ``$name`` substitution (scene.xml:2-9), the perspective sensor with its
 ``to_world`` matrix, ``hdrfilm`` and ``tent`` rfilter (:10-25), BSDF
 declarations with nested ``twosided`` / ``mask`` (:26-219), ``<ref>``, ``obj``
-and ``rectangle`` shapes with ``to_world`` and ``face_normals`` (:221-738) and
-area emitters (:706-731). The result is a plain-dict description; geometry
+``rectangle`` and ``cube`` shapes with ``to_world`` and ``face_normals`` (:221-738) and
+area emitters (:706-731; on a rectangle analytic, on an obj or cube a mesh emitter). The result is a plain-dict description; geometry
 files are referenced, not loaded (the bedroom meshes are Git-LFS pointers and
 are replaced by the deterministic proxy in :mod:`mtx.proxy`).
 """
