@@ -56,6 +56,12 @@ constexpr uint32_t kOccLdsStack = 8;
 #ifndef MTX_SHADE_WARM
 #define MTX_SHADE_WARM 1  // k_shade: warm L2 with the next entry's shading record
 #endif
+#ifndef MTX_SHADE_DEFER
+#define MTX_SHADE_DEFER 0  // k_shade: 1 = stage a step's appends in LDS and flush them a step later (measured: no gain)
+#endif
+#ifndef MTX_SHADOW_PLANES
+#define MTX_SHADOW_PLANES 1  // shadow records as planes of word groups, no x for final-value records (0 = 64-B records)
+#endif
 #ifndef MTX_CACHE_SORT
 #define MTX_CACHE_SORT 2  // NRC cache query order (api.cpp run_cache): 0 as appended, 1 Morton sort, 2 region x XCD
 #endif
@@ -126,6 +132,9 @@ inline size_t stack_ovf_bytes(const DevScene &s) {
 // (non-finite BSDF value / MIS weight), see DESIGN.md. As k_shade stores it
 // for the integrators whose L it stores (kernels.hip make_shadow, flag bit
 // 4): t = the L after an unoccluded ray | flags, x = the L before it.
+// MTX_SHADOW_PLANES (the default): the buffer holds four planes of `capacity`
+// word groups (o | d | t | x) instead of records, and a final-value record
+// has no x (kernels.hip shadow_word).
 constexpr int kFinal = 2;  // the per-path plane of L / misc
 
 struct ShadowRec {

@@ -9,7 +9,8 @@ import json
 import os
 import sys
 
-os.environ["MTX_LIB_VARIANT"] = "stamps"
+# MTX_STAMPS_VARIANT: another stamp build, e.g. "stamps0" for DEFS="-DMTX_DIAG_STAMPS=1 -DMTX_SHADE_DEFER=0"
+os.environ["MTX_LIB_VARIANT"] = os.environ.get("MTX_STAMPS_VARIANT", "stamps")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mitsuba3-experiments_amd"))
 
@@ -19,8 +20,11 @@ SEGS = ["loop top -> shade start (queue entry, prefetched hit)",
         "-> emitter sample (NEE)",
         "-> BSDF eval + sample",
         "-> RR, spawn, path-state stores",
-        "-> block append (2 barriers + 1 atomic) + queue / shadow stores",
-        "-> next step's queue entry and hit"]
+        "-> reservation known to the block (ballots, barrier; MTX_SHADE_DEFER=0: + the atomic's round trip + barrier)",
+        "-> cache-query append, next step's queue entry and hit",
+        "-> queue / shadow stores issued (deferred: the previous step's flush from LDS)",
+        "-> deferred only: second barrier, LDS stage writes, reservation atomic issued"]
+NSEG = len(SEGS)
 
 
 def main():
@@ -34,17 +38,17 @@ def main():
     sc = scene.bedroom()
     integ = PathIntegrator({"max_depth": 8, "rr_depth": 2})
     out = torch.empty((sc.height + 2, sc.width + 2, 4), dtype=torch.float32, device="cuda:0")
-    buf = (C.c_ulonglong * 10)()
+    buf = (C.c_ulonglong * (NSEG + 2))()
     integ.render_film(sc, seed=1, spp=256, out=out)  # warm-up
-    assert lib.mtx_diag_shade_stamps(buf) == 8, "not an MTX_DIAG_STAMPS build"
+    assert lib.mtx_diag_shade_stamps(buf) == NSEG, "not an MTX_DIAG_STAMPS build"
     integ.render_film(sc, seed=0, spp=256, out=out)
     torch.cuda.synchronize()
-    assert lib.mtx_diag_shade_stamps(buf) == 8
-    acc = [int(buf[k]) for k in range(8)]
-    steps, waves = int(buf[8]), int(buf[9])
+    assert lib.mtx_diag_shade_stamps(buf) == NSEG
+    acc = [int(buf[k]) for k in range(NSEG)]
+    steps, waves = int(buf[NSEG]), int(buf[NSEG + 1])
     tot = sum(acc)
-    res = {"steps_per_wave": steps / max(1, waves), "cycles_per_step": tot / max(1, steps),
-           "shares": {SEGS[k]: round(acc[k] / tot, 4) for k in range(8)}}
+    res = {"variant": os.environ["MTX_LIB_VARIANT"], "steps_per_wave": steps / max(1, waves), "cycles_per_step": tot / max(1, steps),
+           "shares": {SEGS[k]: round(acc[k] / tot, 4) for k in range(NSEG)}}
     print(json.dumps(res, indent=1))
 
 
