@@ -474,7 +474,18 @@ int mtx_sample_rays_dev(mtx_ctx *ctx, const mtx_render_args *args, uint64_t n, c
  * 0); any_hit: 0 closest hit (4-wide tree), 1 any hit (8-wide occlusion
  * tree); hits: 4n words
  * (t, prim, u, v) for closest hit, or n words (1 = occluded) for any hit.
- * visits (optional, 2n u32): node and triangle visits. */
+ * visits (optional, 2n u32): node and triangle visits.
+ * The direction need not be normalised (t is in units of |d|), but its
+ * largest component magnitude must lie in [2^-40, 2^60]: the slab tests
+ * replace components below 1e-20 by +-1e-20 (mtx_core/geometry.h
+ * make_trace_ray), which tilts a shorter direction by more than the child
+ * boxes' padding absorbs, and the tree then culls triangles the ray meets
+ * (seen from 2^-50 down on a scene of extent 4; brute force over the
+ * triangles is unaffected). Smaller components beside a largest one in range
+ * are fine, zero and -0 included. d = (0, 0, 0) is allowed and misses.
+ * Non-finite rays are outside the contract (the CPU restatement terminates
+ * and misses on them). Pinned at both ends of the range by
+ * tests/test_lattice.py and tests/test_lattice_gpu.py (class c). */
 int mtx_trace(mtx_ctx *ctx, uint64_t n, const float *rays, int any_hit, uint32_t *hits,
               uint32_t *visits);
 /* mtx_trace on device buffers (Scene.ray_intersect on a device wavefront). */
