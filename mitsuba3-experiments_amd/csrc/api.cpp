@@ -778,7 +778,7 @@ int ensure_wavefront(mtx_ctx *c, uint32_t cap, uint32_t max_depth) {
     if ((rc = dalloc(c->hit, 16ull * cap))) return rc;
     if ((rc = dalloc(c->q0, 4ull * cap))) return rc;
     if ((rc = dalloc(c->q1, 4ull * cap))) return rc;
-    if ((rc = dalloc(c->shadow, sizeof(mtxd::ShadowRec) * (size_t)cap))) return rc;
+    if ((rc = dalloc(c->shadow, 64ull * cap))) return rc;  // four planes of 16-B word groups
     c->capacity = cap;
   }
   if ((rc = dalloc(c->counters, 16ull * (max_depth + 2)))) return rc;
@@ -804,7 +804,7 @@ mtxd::WaveBuffers buffers(mtx_ctx *c) {
   b.hit = (float4 *)c->hit.p;
   b.queue[0] = (uint32_t *)c->q0.p;
   b.queue[1] = (uint32_t *)c->q1.p;
-  b.shadow = (mtxd::ShadowRec *)c->shadow.p;
+  b.shadow = (float4 *)c->shadow.p;
   b.counters = (uint32_t *)c->counters.p;
   b.xheads = (uint32_t *)c->xheads.p;
   b.stats = (unsigned long long *)c->stats.p;
@@ -843,7 +843,7 @@ int ensure_wavefront2(mtx_ctx *c, uint32_t cap, uint32_t max_depth) {
     if ((rc = dalloc(w.pos, 8ull * cap))) return rc;
     if ((rc = dalloc(w.q0, 4ull * cap))) return rc;
     if ((rc = dalloc(w.q1, 4ull * cap))) return rc;
-    if ((rc = dalloc(w.shadow, sizeof(mtxd::ShadowRec) * (size_t)cap))) return rc;
+    if ((rc = dalloc(w.shadow, 64ull * cap))) return rc;  // four planes of 16-B word groups
     w.capacity = cap;
   }
   if ((rc = dalloc(w.counters, 16ull * (max_depth + 2)))) return rc;
@@ -870,7 +870,7 @@ mtxd::WaveBuffers buffers2(mtx_ctx *c) {
   b.hit = (float4 *)w.hit.p;
   b.queue[0] = (uint32_t *)w.q0.p;
   b.queue[1] = (uint32_t *)w.q1.p;
-  b.shadow = (mtxd::ShadowRec *)w.shadow.p;
+  b.shadow = (float4 *)w.shadow.p;
   b.counters = (uint32_t *)w.counters.p;
   b.xheads = (uint32_t *)w.xheads.p;
   b.capacity = w.capacity;

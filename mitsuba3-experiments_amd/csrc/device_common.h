@@ -261,34 +261,6 @@ __device__ __forceinline__ void block_append2(bool p0, bool p1, bool p1_hi, uint
              : ol + __builtin_amdgcn_mbcnt_hi((uint32_t)(ml >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ml, 0u));
 }
 
-// LDS stage of one block step's appended records (k_shade with
-// MTX_SHADE_DEFER): block_append2's single reservation atomic is issued at the
-// end of the step and its result is consumed one step later, so no wave waits
-// for the round trip. The step's records wait here at their block-local
-// compacted offsets; the next step's flush moves entry `tid` of every plane to
-// `base + tid` of its queue, in block_append2's in-range order (the p1_hi
-// entries of the second queue after the others).
-//   st    the next ray / state planes (ray_o, ray_d, thr, prev, L, misc)
-//   sh    the shadow record's word groups (o, d, t; x without MTX_SHADOW_PLANES)
-//   wcnt  the waves' counts of the three ballots
-//   pub   the step being flushed: first queue's base, second queue's base,
-//         entries of the first, entries of the second
-// One instance per block (37 KB, 41 KB with x: three blocks per CU fit the 160 KB).
-constexpr int kShadowWords = MTX_SHADOW_PLANES ? 3 : 4;
-template <int BLOCK>
-struct ShadeStage {
-  float4 st[6][BLOCK];
-  float4 sh[kShadowWords][BLOCK];
-  uint32_t path[BLOCK];
-  uint32_t wcnt[3][BLOCK / 64];
-  uint32_t pub[4];
-};
-template <int BLOCK>
-__device__ __forceinline__ ShadeStage<BLOCK> &shade_stage() {
-  __shared__ ShadeStage<BLOCK> sg;
-  return sg;
-}
-
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
   return v;

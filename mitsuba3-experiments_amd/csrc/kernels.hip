@@ -115,37 +115,27 @@ __device__ __forceinline__ void apply_shadow(float4 &L, float4 rt, float4 rx, bo
   }
 }
 
-// Any-hit traversal of the NEE shadow rays. k_shade stores each record of
-// the integrators whose L it stores itself (path-mis, path, nrc, pssmltpath)
-// in its final-value form (make_shadow with Lcur, flag kShadowFinal): t = the path's L after an unoccluded
-// ray (fma(T, X, L), path-mis.py:117, or L + X, path.py:259 / nrc.py:62) with
-// the flags in t.w, x = the path's L before it. The finish is one store -- no
-// read of L: t.xyz with x.w when unoccluded; when occluded, nothing unless a
-// flagged channel must become NaN (then x, read from the record, with those
-// channels NaN). With MTX_SHADOW_PLANES (below) x is not stored at all.
+// Any-hit traversal of the NEE shadow rays. The records lie as planes of word
+// groups (wavefront.h). k_shade stores each record of the integrators whose L
+// it stores itself (path-mis, path, nrc, pssmltpath) in its final-value form
+// (make_shadow with Lcur, flag kShadowFinal): t = the path's L after an
+// unoccluded ray (fma(T, X, L), path-mis.py:117, or L + X, path.py:259 /
+// nrc.py:62) with the flags in t.w, and no x: the record's target already
+// holds the L before the ray, L.w included (k_shade stored it there in the
+// same launch that wrote the record). The unoccluded finish stores t.xyz
+// alone (12 B, no read of L, L.w stays); the occluded one does nothing unless
+// a flagged channel must become NaN (then it reads L from the target). The x
+// plane is the read-modify-write form's (the nerad integrators).
 constexpr uint32_t kShadowFinal = 16u;  // record flag: final-value form
-// MTX_SHADOW_PLANES (wavefront.h): the records lie as planes of word groups
-// over the same allocation, and a final-value record has no x: its target
-// already holds the L before the ray, L.w included (k_shade stored it there in
-// the same launch that wrote the record). The unoccluded finish then stores
-// t.xyz alone (12 B, L.w stays), the rare occluded one with NaN flags reads L
-// from the target; the x plane is the read-modify-write form's.
 // Word group g (0 o, 1 d | L index, 2 t | flags, 3 x) of record k:
 __device__ __forceinline__ float4 *shadow_word(const WaveBuffers &b, uint32_t g, uint32_t k) {
-#if MTX_SHADOW_PLANES
-  return reinterpret_cast<float4 *>(b.shadow) + ((size_t)g * b.capacity + k);
-#else
-  return reinterpret_cast<float4 *>(b.shadow + k) + g;
-#endif
+  return b.shadow + ((size_t)g * b.capacity + k);
 }
 
 struct ShadowSrc {
   struct Payload {
     uint32_t k, li;  // record, L index of the target (plane * capacity + position)
     float4 t;        // L after an unoccluded ray | flags
-#if !MTX_SHADOW_PLANES
-    float lw;        // L.w (unchanged by the update)
-#endif
   };
   WaveBuffers b;
   __device__ __forceinline__ void load(uint32_t k, TraceRay &r, float &tmax, Payload &pl) const {
@@ -155,9 +145,6 @@ struct ShadowSrc {
     pl.k = k;
     pl.li = __float_as_uint(d4.w);
     pl.t = ld_stream<kNtTrace>(shadow_word(b, 2, k));
-#if !MTX_SHADOW_PLANES
-    pl.lw = shadow_word(b, 3, k)->w;
-#endif
   }
   __device__ __forceinline__ void finish(const Payload &pl, bool occluded, float, uint32_t, float, float) const {
     const uint32_t fl = __float_as_uint(pl.t.w);
@@ -171,18 +158,10 @@ struct ShadowSrc {
       return;
     }
     if (!occluded) {
-#if MTX_SHADOW_PLANES
       typedef float v3f __attribute__((ext_vector_type(3)));
       *reinterpret_cast<v3f *>(b.L[0] + pl.li) = v3f{pl.t.x, pl.t.y, pl.t.z};
-#else
-      st_stream<kNtTraceSt>(b.L[0] + pl.li, make_float4(pl.t.x, pl.t.y, pl.t.z, pl.lw));
-#endif
     } else if (fl & 14u) {
-#if MTX_SHADOW_PLANES
       float4 L = b.L[0][pl.li];
-#else
-      float4 L = *shadow_word(b, 3, pl.k);
-#endif
       const float qnan = __uint_as_float(0x7fc00000u);
       if (fl & 2u) L.x = qnan;
       if (fl & 4u) L.y = qnan;
@@ -278,16 +257,22 @@ __global__ void k_raygen_rays(DevScene s, WaveBuffers b, ChunkParams p, const fl
 // Diagnostic build only (MTX_DIAG_STAMPS=1, tools/shade_stamps.py): s_memtime
 // stamps between the phases of a shade step, summed per wave in scalar
 // registers and added to g_shade_stamps at the kernel's end. Read shares, not
-// the build's run time (cdna_hip_programming.md "In-kernel stamps").
+// the build's run time (cdna_hip_programming.md "In-kernel stamps"). In the
+// default build Stamps is empty and the three macros expand to nothing, so
+// their call sites are plain statements: MTX_STAMP_BEGIN(st) starts the clock
+// at the kernel's top, MTX_STAMP(st, i) ends segment i (the segments are
+// numbered in the order a step runs them; tools/shade_stamps.py names them),
+// MTX_STAMP_STEP(st) is segment 0's stamp at the loop top and counts the step.
 #ifndef MTX_DIAG_STAMPS
 #define MTX_DIAG_STAMPS 0
 #endif
-constexpr int kStampSegs = 10;
-struct Stamps {
-  unsigned long long prev, acc[kStampSegs];
-};
 #if MTX_DIAG_STAMPS
+constexpr int kStampSegs = 9;
+struct Stamps {
+  unsigned long long prev, acc[kStampSegs], steps;
+};
 __device__ unsigned long long g_shade_stamps[kStampSegs + 2];
+#define MTX_STAMP_BEGIN(st) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"((st).prev)::"memory")
 #define MTX_STAMP(st, i)                                                                  \
   do {                                                                                    \
     unsigned long long t_;                                                                \
@@ -297,7 +282,27 @@ __device__ unsigned long long g_shade_stamps[kStampSegs + 2];
     (st).acc[i] += t_ - (st).prev;                                                        \
     (st).prev = t_;                                                                       \
   } while (0)
+#define MTX_STAMP_STEP(st) \
+  do {                     \
+    ++(st).steps;          \
+    MTX_STAMP(st, 0);      \
+  } while (0)
+#else
+struct Stamps {};
+#define MTX_STAMP_BEGIN(st) ((void)0)
+#define MTX_STAMP(st, i) ((void)0)
+#define MTX_STAMP_STEP(st) ((void)0)
 #endif
+
+// The shadow record as shade_* builds it in registers (make_shadow); k_shade
+// stores its word groups to the planes of WaveBuffers::shadow (shadow_word),
+// the megakernels apply it at once (apply_shadow_rec).
+struct ShadowRec {
+  float4 o;
+  float4 d;
+  float4 t;
+  float4 x;
+};
 
 struct ShadeIO {
   ShadowRec rec;
@@ -308,10 +313,8 @@ struct ShadeIO {
   float4 nro, nrd, nthr, nprev;  // the next ray and state: k_shade stores them at the path's append slot
   float4 nL;                     // result and sampler state: at the append slot, or by path once the path ends
   uint4 nmisc;
-  float warm;                    // MTX_SHADE_WARM: the next entry's shading-record word (L2 warm-up)
-#if MTX_DIAG_STAMPS
-  Stamps st;
-#endif
+  float warm;                    // the next entry's shading-record word (L2 warm-up)
+  Stamps st;                     // k_shade's stamps while the shade runs (empty unless MTX_DIAG_STAMPS)
 };
 
 // Which shadow-record form an integrator's NEE must use (ShadowSrc::finish
@@ -437,11 +440,9 @@ __device__ __forceinline__ bool shade_path(const DevScene &s, const SceneView &s
   float prev_pdf = Lr.w;
   const V3 ray_d = V3{rd.x, rd.y, rd.z};
   const SurfaceInteraction si = compute_si_dev(s, h.x, __float_as_uint(h.y), h.z, h.w, ray_d);
-#if MTX_DIAG_STAMPS
   MTX_STAMP(io.st, 1);
-#endif
   // the next queue entry's shading record, one word: its line is in L2 when
-  // the next iteration reads the record (k_shade, MTX_SHADE_WARM)
+  // the next iteration reads the record (k_shade)
   if (warm) io.warm = warm->x;
   if (kPrevOnEmitter && bounce != 0 && si.emitter >= 0) pv = b.prev[rp][qi];
   V3 prev_p = V3{pv.x, pv.y, pv.z};
@@ -534,9 +535,7 @@ __device__ __forceinline__ bool shade_path(const DevScene &s, const SceneView &s
   const mtx_material mat = sv.materials[si.material];
   // before the emitter sample; the NEE eval and the BSDF sample both read it
   const BsdfData bd = bsdf_at(sv, mat, si.uv);
-#if MTX_DIAG_STAMPS
   MTX_STAMP(io.st, 2);
-#endif
   const bool smooth = (bsdf_flags(mat) & BF_SMOOTH) != 0;
   bool active_em = (INT == MTX_INT_PATH_MIS ? active_next : true) && smooth;
   const V2 u_em = rng.next_2d();
@@ -550,9 +549,7 @@ __device__ __forceinline__ bool shade_path(const DevScene &s, const SceneView &s
   V3 em_weight = v3s(0.f);
   const bool do_nee = (INT == MTX_INT_NRC) ? true : active_em;  // nrc.py:51-53 samples with `active`
   if (do_nee) em_weight = sample_emitter_direction(sv, si.p, u_em, &ds);
-#if MTX_DIAG_STAMPS
   MTX_STAMP(io.st, 3);
-#endif
   if (INT != MTX_INT_PATH_MIS) active_em = active_em && ds.pdf != 0.f;
   const V3 wo = to_local(si.sh, ds.d);
   const float s1 = rng.next_1d();
@@ -563,9 +560,7 @@ __device__ __forceinline__ bool shade_path(const DevScene &s, const SceneView &s
   // eval / pdf only feed the NEE contribution (no draws, no side effects)
   if (active_em) bsdf_eval_pdf(bd, mat, si.uv, si.wi, wo, &bsdf_val, &bsdf_pdf);
   const V3 bsdf_weight = bsdf_sample(bd, mat, si.uv, si.wi, s1, s2, &bs);
-#if MTX_DIAG_STAMPS
   MTX_STAMP(io.st, 4);
-#endif
 
   if (INT == MTX_INT_PATH_MIS) {
     const float mi_em = mis_weight_b(ds.pdf, bsdf_pdf);
@@ -634,9 +629,7 @@ __device__ __forceinline__ bool shade_path(const DevScene &s, const SceneView &s
   io.nprev = make_float4(prev_p.x, prev_p.y, prev_p.z, spread);
   io.nL = make_float4(L.x, L.y, L.z, (INT == MTX_INT_PATH_MIS && !active) ? end_w(flags, prev_pdf) : prev_pdf);
   io.nmisc = make_uint4((uint32_t)rng.state, (uint32_t)(rng.state >> 32), rng.seq, depth | (flags << 16));
-#if MTX_DIAG_STAMPS
   MTX_STAMP(io.st, 5);
-#endif
   return active;
 }
 
@@ -987,44 +980,6 @@ __device__ __forceinline__ bool shade_nerad(const DevScene &s, const SceneView &
   return false;
 }
 
-// MTX_SHADE_DEFER: moves the staged records of one block step to their queue
-// slots, entry `tid` of every plane to `base + tid` (whole 16-B stores at
-// consecutive slots; sg.pub holds the step's bases and counts, all zero for a
-// step that appended nothing). `np` is the next bounce's ray / state plane.
-constexpr uint32_t kShadowStaged = 32u;  // staged record flag: d.w is the path's block-local append offset
-template <int INT>
-__device__ __forceinline__ void shade_flush(const WaveBuffers &b, const ShadeStage<kShadeBlock> &sg, uint32_t *out_q,
-                                            uint32_t np) {
-  static_assert(shadow_final_form(INT), "the deferred append stages the state planes k_shade stores for these");
-  const uint32_t tid = threadIdx.x;
-  const uint32_t b0 = sg.pub[0], b1 = sg.pub[1], n0 = sg.pub[2], ns = sg.pub[3];
-  if (tid < n0) {
-    const uint32_t slot = b0 + tid;
-    st_stream<kNtQueue>(out_q + slot, sg.path[tid]);
-    st_stream<kNtShadeSt>(b.ray_o[np] + slot, sg.st[0][tid]);
-    st_stream<kNtShadeSt>(b.ray_d[np] + slot, sg.st[1][tid]);
-    st_stream<kNtShadeSt>(b.thr[np] + slot, sg.st[2][tid]);
-    st_stream<kNtShadeSt>(b.prev[np] + slot, sg.st[3][tid]);
-    st_stream<kNtShadeSt>(b.L[np] + slot, sg.st[4][tid]);
-    const float4 m = sg.st[5][tid];
-    st_stream<kNtShadeSt>(b.misc[np] + slot, make_uint4(__float_as_uint(m.x), __float_as_uint(m.y),
-                                                        __float_as_uint(m.z), __float_as_uint(m.w)));
-  }
-  if (tid < ns) {
-    float4 d = sg.sh[1][tid], t = sg.sh[2][tid];
-    const uint32_t fl = __float_as_uint(t.w);
-    if (fl & kShadowStaged) {  // a continuing path's record: its L is at the path's append slot
-      d.w = __uint_as_float(np * b.capacity + b0 + __float_as_uint(d.w));
-      t.w = __uint_as_float(fl & ~kShadowStaged);
-    }
-    const uint32_t k = b1 + tid;
-    st_stream<kNtShadeSt>(shadow_word(b, 0, k), sg.sh[0][tid]);
-    st_stream<kNtShadeSt>(shadow_word(b, 1, k), d);
-    st_stream<kNtShadeSt>(shadow_word(b, 2, k), t);
-    if constexpr (!MTX_SHADOW_PLANES) st_stream<kNtShadeSt>(shadow_word(b, 3, k), sg.sh[kShadowWords - 1][tid]);
-  }
-}
-
 // blocks per CU the shade kernels are built for (their register budget):
 // kShadeMinBlocks for every integrator (pssmltpath.py's shade at 2 blocks,
 // without its spills, measured slower: DESIGN.md §7)
@@ -1042,18 +997,6 @@ __global__ __launch_bounds__(kShadeBlock, kShadeMinBlocks) void k_shade(DevScene
   constexpr bool kNerad = INT == MTX_INT_NERAD_RHS || INT == MTX_INT_NERAD;
   const uint32_t stride = gridDim.x * kShadeBlock;
   uint32_t parity = 0;
-  // MTX_SHADE_DEFER: the integrators whose L k_shade stores stage a step's
-  // appends in LDS and flush them one step later (ShadeStage); `pend` is the
-  // reservation in flight, thread 0's. The others keep block_append2.
-  constexpr bool kDefer = MTX_SHADE_DEFER != 0 && shadow_final_form(INT);
-  unsigned long long pend = 0;
-  if constexpr (kDefer) {
-    if (threadIdx.x == 0) {
-      ShadeStage<kShadeBlock> &sg = shade_stage<kShadeBlock>();
-      sg.pub[2] = 0u;
-      sg.pub[3] = 0u;
-    }
-  }
   // software pipeline over the persistent loop: the next step's queue entry
   // loads during this step, its hit record before this step's appends. Hit
   // records are stored by queue position (ClosestSrc), so they load
@@ -1068,34 +1011,26 @@ __global__ __launch_bounds__(kShadeBlock, kShadeMinBlocks) void k_shade(DevScene
     h = ld_stream<kNtShade>(b.hit + i0);
   }
 
-#if MTX_DIAG_STAMPS
   Stamps stp{};
-  unsigned long long steps = 0;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stp.prev)::"memory");
-#endif
+  MTX_STAMP_BEGIN(stp);
   for (uint32_t base = blockIdx.x * kShadeBlock; base < count; base += stride, parity ^= 1u) {
     const uint32_t i = base + threadIdx.x;
     const uint32_t inext = i + stride;
     uint32_t path_n = 0;
     if (inext < count) path_n = ident ? inext : ld_stream<kNtQueue>(in_q + inext);
-#if MTX_SHADE_WARM
+    // the next step's hit record, and from it the address of the shading
+    // record that step will read: shade_path touches one word of it (L2 warm-up)
     float4 hn = make_float4(0.f, 0.f, 0.f, 0.f);
     if (inext < count) hn = b.hit[inext];
     const uint32_t pn = __float_as_uint(hn.y);
     const float4 *wp = (inext < count && pn != 0xffffffffu) ? s.shade_rec + 8 * (size_t)pn : nullptr;
-#else
-    const float4 *wp = nullptr;
-#endif
     ShadeIO io;
     io.emit = false;
     io.em_hi = false;
     io.query = false;
     io.warm = 0.f;
-#if MTX_DIAG_STAMPS
-    ++steps;
-    MTX_STAMP(stp, 0);
+    MTX_STAMP_STEP(stp);
     io.st = stp;
-#endif
     bool cont = false;
     const bool valid = i < count;
     if (valid) {
@@ -1115,157 +1050,42 @@ __global__ __launch_bounds__(kShadeBlock, kShadeMinBlocks) void k_shade(DevScene
     (void)wp;
     const uint32_t path_c = path;
     path = path_n;
-#if MTX_SHADE_WARM
     h = hn;
     asm volatile("" ::"v"(io.warm));  // the warm-up load completes in this iteration
-    // MTX_SHADE_DEFER: so do the next step's queue entry and hit record, here
-    // on every path. A wave that skipped the shade otherwise leaves them to a
-    // vmcnt(0) at the loop's end, which would wait for the reservation just
-    // issued (direct append: shade +1.4 ms per step with this wait moved here)
-    if constexpr (kDefer) asm volatile("" ::"v"(path), "v"(h.y), "v"(h.z), "v"(h.w));
-#else
-    if (inext < count) h = ld_stream<kNtShade>(b.hit + inext);
-#endif
-
-#if MTX_DIAG_STAMPS
     stp = io.st;
-#endif
-    if constexpr (kDefer) {
-      // deferred append: this step's reservation atomic is issued at the end
-      // of the step and its result is read one step later (`pend`), so its
-      // round trip overlaps the next step's loads; the records wait in LDS
-      ShadeStage<kShadeBlock> &sg = shade_stage<kShadeBlock>();
-      constexpr uint32_t W = kShadeBlock / 64;
-      const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-      const bool em_lo = io.emit && !io.em_hi, em_hi = io.emit && io.em_hi;
-      const uint64_t m0 = __ballot(cont), ml = __ballot(em_lo), mh = __ballot(em_hi);
-      if (lane == 0) {
-        sg.wcnt[0][wave] = (uint32_t)__popcll(m0);
-        sg.wcnt[1][wave] = (uint32_t)__popcll(ml);
-        sg.wcnt[2][wave] = (uint32_t)__popcll(mh);
+
+    uint32_t slot, sslot;
+    block_append2<kShadeBlock>(cont, io.emit, io.emit && io.em_hi, out_cnt, parity, slot, sslot);
+    MTX_STAMP(stp, 6);
+    if (cont) {
+      st_stream<kNtQueue>(out_q + slot, path_c);
+      st_stream<kNtShadeSt>(b.ray_o[rp ^ 1u] + slot, io.nro);
+      st_stream<kNtShadeSt>(b.ray_d[rp ^ 1u] + slot, io.nrd);
+      if constexpr (!kNerad) st_stream<kNtShadeSt>(b.thr[rp ^ 1u] + slot, io.nthr);
+      if constexpr (INT == MTX_INT_PATH_MIS || INT == MTX_INT_PATH || INT == MTX_INT_NRC || INT == MTX_INT_PSSMLT_PATH)
+        st_stream<kNtShadeSt>(b.prev[rp ^ 1u] + slot, io.nprev);
+      if constexpr (!kNerad) {
+        st_stream<kNtShadeSt>(b.L[rp ^ 1u] + slot, io.nL);
+        st_stream<kNtShadeSt>(b.misc[rp ^ 1u] + slot, io.nmisc);
       }
-      // a path that ends needs no slot: its L / misc go to the final plane now
-      if (!cont && valid) {
-        st_stream<kNtShadeSt>(b.L[kFinal] + path_c, io.nL);
-        if (!p.drop_end_misc) st_stream<kNtShadeSt>(b.misc[kFinal] + path_c, io.nmisc);
-      }
-      if (threadIdx.x == 0) {  // the previous step's reservation (issued one step ago)
-        sg.pub[0] = (uint32_t)pend;
-        sg.pub[1] = (uint32_t)(pend >> 32);
-      }
-      __syncthreads();
-#if MTX_DIAG_STAMPS
-      MTX_STAMP(stp, 6);
-#endif
-      shade_flush<INT>(b, sg, out_q, rp ^ 1u);
-      uint32_t o0 = 0, ol = 0, oh = 0, t0 = 0, tl = 0, th = 0;
-#pragma unroll
-      for (uint32_t w = 0; w < W; ++w) {
-        const uint32_t c0 = sg.wcnt[0][w], cl = sg.wcnt[1][w], ch = sg.wcnt[2][w];
-        if (w < wave) {
-          o0 += c0;
-          ol += cl;
-          oh += ch;
-        }
-        t0 += c0;
-        tl += cl;
-        th += ch;
-      }
-      const uint32_t l0 = o0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, 0u));
-      const uint32_t ls =
-          io.em_hi ? tl + oh + __builtin_amdgcn_mbcnt_hi((uint32_t)(mh >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mh, 0u))
-                   : ol + __builtin_amdgcn_mbcnt_hi((uint32_t)(ml >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ml, 0u));
-#if MTX_DIAG_STAMPS
-      MTX_STAMP(stp, 8);
-#endif
-      __syncthreads();
-      if (cont) {
-        sg.path[l0] = path_c;
-        sg.st[0][l0] = io.nro;
-        sg.st[1][l0] = io.nrd;
-        sg.st[2][l0] = io.nthr;
-        sg.st[3][l0] = io.nprev;
-        sg.st[4][l0] = io.nL;
-        sg.st[5][l0] = make_float4(__uint_as_float(io.nmisc.x), __uint_as_float(io.nmisc.y),
-                                   __uint_as_float(io.nmisc.z), __uint_as_float(io.nmisc.w));
-      }
-      if (io.emit) {
-        // the L index of a continuing path's record depends on the path's
-        // append slot: staged as its block-local offset with kShadowStaged in
-        // the flags, completed by the flush once the base is known
-        uint32_t fl = __float_as_uint(io.rec.t.w);
-        if (cont) {
-          io.rec.d.w = __uint_as_float(l0);
-          fl |= kShadowStaged;
-        } else {
-          io.rec.d.w = __uint_as_float(kFinal * b.capacity + path_c);
-        }
-        io.rec.t.w = __uint_as_float(fl);
-        sg.sh[0][ls] = io.rec.o;
-        sg.sh[1][ls] = io.rec.d;
-        sg.sh[2][ls] = io.rec.t;
-        if constexpr (!MTX_SHADOW_PLANES) {
-          io.rec.x.w = io.nL.w;  // final-value form: L.w (set after the NEE)
-          sg.sh[kShadowWords - 1][ls] = io.rec.x;
-        }
-      }
-      if (threadIdx.x == 0) {
-        // a step that appends nothing issues no atomic: its flush is a no-op
-        // (the pointer passes through an empty asm so that it counts as
-        // per-lane: for a wave-uniform pointer the compiler rewrites the
-        // atomic as a wave reduction whose readfirstlane waits for the result
-        // right here, the wait this branch exists to move)
-        if (t0 | tl | th) {
-          typedef __attribute__((address_space(1))) unsigned long long gu64;  // global: no flat atomic
-          gu64 *cp = (gu64 *)reinterpret_cast<unsigned long long *>(out_cnt);
-          asm volatile("" : "+v"(cp));
-          pend = __hip_atomic_fetch_add(cp, ((unsigned long long)(tl + th) << 32) | t0, __ATOMIC_RELAXED,
-                                        __HIP_MEMORY_SCOPE_AGENT);  // = atomicAdd
-        }
-        sg.pub[2] = t0;
-        sg.pub[3] = tl + th;
-      }
-    } else {
-      uint32_t slot, sslot;
-      block_append2<kShadeBlock>(cont, io.emit, io.emit && io.em_hi, out_cnt, parity, slot, sslot);
-#if MTX_DIAG_STAMPS
-      MTX_STAMP(stp, 6);
-#endif
-      if (cont) {
-        st_stream<kNtQueue>(out_q + slot, path_c);
-        st_stream<kNtShadeSt>(b.ray_o[rp ^ 1u] + slot, io.nro);
-        st_stream<kNtShadeSt>(b.ray_d[rp ^ 1u] + slot, io.nrd);
-        if constexpr (!kNerad) st_stream<kNtShadeSt>(b.thr[rp ^ 1u] + slot, io.nthr);
-        if constexpr (INT == MTX_INT_PATH_MIS || INT == MTX_INT_PATH || INT == MTX_INT_NRC || INT == MTX_INT_PSSMLT_PATH)
-          st_stream<kNtShadeSt>(b.prev[rp ^ 1u] + slot, io.nprev);
-        if constexpr (!kNerad) {
-          st_stream<kNtShadeSt>(b.L[rp ^ 1u] + slot, io.nL);
-          st_stream<kNtShadeSt>(b.misc[rp ^ 1u] + slot, io.nmisc);
-        }
-      } else if (!kNerad && valid) {
-        st_stream<kNtShadeSt>(b.L[kFinal] + path_c, io.nL);
-        if (!p.drop_end_misc) st_stream<kNtShadeSt>(b.misc[kFinal] + path_c, io.nmisc);
-      }
-      if (io.emit) {
-        // the contribution goes to the path's L where the next shade (or the
-        // film) reads it; the integrators that emit shadow rays (path-mis,
-        // path, nrc, pssmltpath; not the nerad ones) store io.nL there
-        const uint32_t li = (kNerad || !cont) ? kFinal * b.capacity + path_c : (rp ^ 1u) * b.capacity + slot;
-        io.rec.d.w = __uint_as_float(li);
-        if constexpr (!kNerad) io.rec.x.w = io.nL.w;  // final-value form: L.w (set after the NEE)
-        st_stream<kNtShadeSt>(shadow_word(b, 0, sslot), io.rec.o);
-        st_stream<kNtShadeSt>(shadow_word(b, 1, sslot), io.rec.d);
-        st_stream<kNtShadeSt>(shadow_word(b, 2, sslot), io.rec.t);
-        // a final-value record's x is its target's L, stored above
-        if constexpr (kNerad || !MTX_SHADOW_PLANES) st_stream<kNtShadeSt>(shadow_word(b, 3, sslot), io.rec.x);
-      }
-#if MTX_DIAG_STAMPS
-      MTX_STAMP(stp, 8);
-#endif
+    } else if (!kNerad && valid) {
+      st_stream<kNtShadeSt>(b.L[kFinal] + path_c, io.nL);
+      if (!p.drop_end_misc) st_stream<kNtShadeSt>(b.misc[kFinal] + path_c, io.nmisc);
     }
-#if MTX_DIAG_STAMPS
-    MTX_STAMP(stp, 9);
-#endif
+    if (io.emit) {
+      // the contribution goes to the path's L where the next shade (or the
+      // film) reads it; the integrators that emit shadow rays (path-mis,
+      // path, nrc, pssmltpath; not the nerad ones) store io.nL there
+      const uint32_t li = (kNerad || !cont) ? kFinal * b.capacity + path_c : (rp ^ 1u) * b.capacity + slot;
+      io.rec.d.w = __uint_as_float(li);
+      if constexpr (!kNerad) io.rec.x.w = io.nL.w;  // final-value form: L.w (set after the NEE)
+      st_stream<kNtShadeSt>(shadow_word(b, 0, sslot), io.rec.o);
+      st_stream<kNtShadeSt>(shadow_word(b, 1, sslot), io.rec.d);
+      st_stream<kNtShadeSt>(shadow_word(b, 2, sslot), io.rec.t);
+      // a final-value record has no x: it is its target's L, stored above
+      if constexpr (kNerad) st_stream<kNtShadeSt>(shadow_word(b, 3, sslot), io.rec.x);
+    }
+    MTX_STAMP(stp, 7);
     if constexpr (INT == MTX_INT_NRC || INT == MTX_INT_NERAD_RHS || INT == MTX_INT_NERAD) {
       if (INT != MTX_INT_NRC || p.nrc_cache) {
         const uint32_t q = block_reserve<kShadeBlock>(io.query ? 1u : 0u, b.cq_count);
@@ -1276,23 +1096,12 @@ __global__ __launch_bounds__(kShadeBlock, kShadeMinBlocks) void k_shade(DevScene
         }
       }
     }
-#if MTX_DIAG_STAMPS
-    MTX_STAMP(stp, 7);
-#endif
-  }
-  if constexpr (kDefer) {  // the last step's records (a block without steps flushes nothing)
-    ShadeStage<kShadeBlock> &sg = shade_stage<kShadeBlock>();
-    if (threadIdx.x == 0) {
-      sg.pub[0] = (uint32_t)pend;
-      sg.pub[1] = (uint32_t)(pend >> 32);
-    }
-    __syncthreads();
-    shade_flush<INT>(b, sg, out_q, rp ^ 1u);
+    MTX_STAMP(stp, 8);
   }
 #if MTX_DIAG_STAMPS
   if ((threadIdx.x & 63u) == 0) {
     for (int k = 0; k < kStampSegs; ++k) atomicAdd(&g_shade_stamps[k], stp.acc[k]);
-    atomicAdd(&g_shade_stamps[kStampSegs], steps);
+    atomicAdd(&g_shade_stamps[kStampSegs], stp.steps);
     atomicAdd(&g_shade_stamps[kStampSegs + 1], 1ull);
   }
 #endif

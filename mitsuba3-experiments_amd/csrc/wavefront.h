@@ -19,7 +19,8 @@
 // kernels). pos is per path, hit per queue position. Paths of a chunk are
 // pixel-major: path = q * spp + s for sample s of the chunk's pixel q.
 // Queues are u32 path indices compacted per 256-thread block (ballot + mbcnt
-// + LDS, one atomic per block step); shadow rays are 64-byte records.
+// + LDS, one atomic per block step); shadow rays are four planes of 16-byte
+// word groups, indexed by their own queue position.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -52,15 +53,6 @@ constexpr uint32_t kOccLdsStack = 8;
 #endif
 #ifndef MTX_OCC_LDS_TOP
 #define MTX_OCC_LDS_TOP 48  // occlusion tree nodes copied into LDS per trace block (0 = none)
-#endif
-#ifndef MTX_SHADE_WARM
-#define MTX_SHADE_WARM 1  // k_shade: warm L2 with the next entry's shading record
-#endif
-#ifndef MTX_SHADE_DEFER
-#define MTX_SHADE_DEFER 0  // k_shade: 1 = stage a step's appends in LDS and flush them a step later (measured: no gain)
-#endif
-#ifndef MTX_SHADOW_PLANES
-#define MTX_SHADOW_PLANES 1  // shadow records as planes of word groups, no x for final-value records (0 = 64-B records)
 #endif
 #ifndef MTX_CACHE_SORT
 #define MTX_CACHE_SORT 2  // NRC cache query order (api.cpp run_cache): 0 as appended, 1 Morton sort, 2 region x XCD
@@ -124,25 +116,19 @@ inline size_t stack_ovf_bytes(const DevScene &s) {
   return n > 8 ? n : 8;
 }
 
-// Shadow-ray record (64 B): o.xyz maxt | d.xyz L index | t | x (L index =
-// plane * capacity + position of the path's L, WaveBuffers). As make_shadow
-// builds it: t = T.xyz flags, x = X.xyz 0; flags bit0: fma form
-// L = fma(T, X, L) (path-mis.py:117) else L = L + X (path.py:259, nrc.py:62);
-// bits 1..3: the occluded-case contribution of that channel is NaN
-// (non-finite BSDF value / MIS weight), see DESIGN.md. As k_shade stores it
-// for the integrators whose L it stores (kernels.hip make_shadow, flag bit
-// 4): t = the L after an unoccluded ray | flags, x = the L before it.
-// MTX_SHADOW_PLANES (the default): the buffer holds four planes of `capacity`
-// word groups (o | d | t | x) instead of records, and a final-value record
-// has no x (kernels.hip shadow_word).
+// Shadow rays (WaveBuffers::shadow): four planes of `capacity` 16-B word
+// groups, o | d | t | x, record k at position k of each plane (kernels.hip
+// shadow_word): o.xyz maxt | d.xyz L index | t | x (L index = plane *
+// capacity + position of the path's L, WaveBuffers). Two forms, told apart
+// by flag bit 4 of t.w (kernels.hip make_shadow):
+//   read-modify-write (the nerad integrators): t = T.xyz flags, x = X.xyz 0;
+//     flags bit0: fma form L = fma(T, X, L) (path-mis.py:117) else L = L + X
+//     (path.py:259, nrc.py:62); bits 1..3: the occluded-case contribution of
+//     that channel is NaN (non-finite BSDF value / MIS weight), see DESIGN.md.
+//   final-value (the integrators whose L k_shade stores): t = the L after an
+//     unoccluded ray | flags; no x is stored, the L before the ray is already
+//     at the record's target.
 constexpr int kFinal = 2;  // the per-path plane of L / misc
-
-struct ShadowRec {
-  float4 o;
-  float4 d;
-  float4 t;
-  float4 x;
-};
 
 struct WaveBuffers {
   // rays of bounce b at ray_o / ray_d[(b + ray_par) & 1][k] for queue position
@@ -164,7 +150,7 @@ struct WaveBuffers {
   float2 *pos;
   float4 *hit;
   uint32_t *queue[2];
-  ShadowRec *shadow;
+  float4 *shadow;       // four planes of `capacity` word groups: o | d | t | x (above)
   uint32_t *counters;   // per bounce b: [4b+0] rays of bounce b, [4b+1] shadow rays of bounce b-1 (one 8-B pair with the queue shade b-1 fills), [4b+2], [4b+3] unused
   uint32_t *xheads;     // per bounce b: slot 2b closest-hit, 2b+1 shadow claim cursors (kXSlotWords each)
   unsigned long long *stats;  // nodes_c, tris_c, nodes_s, tris_s, rays_c, rays_s

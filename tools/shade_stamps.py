@@ -9,21 +9,21 @@ import json
 import os
 import sys
 
-# MTX_STAMPS_VARIANT: another stamp build, e.g. "stamps0" for DEFS="-DMTX_DIAG_STAMPS=1 -DMTX_SHADE_DEFER=0"
+# MTX_STAMPS_VARIANT: another stamp build (`make variant NAME=<it>` with -DMTX_DIAG_STAMPS=1 among its DEFS)
 os.environ["MTX_LIB_VARIANT"] = os.environ.get("MTX_STAMPS_VARIANT", "stamps")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mitsuba3-experiments_amd"))
 
+# segment k ends at MTX_STAMP(.., k) of kernels.hip, in the order a step runs them
 SEGS = ["loop top -> shade start (queue entry, prefetched hit)",
         "-> surface interaction (ray_d, thr, L, misc, shading record)",
         "-> material + texture colour (bsdf_at)",
         "-> emitter sample (NEE)",
         "-> BSDF eval + sample",
         "-> RR, spawn, path-state stores",
-        "-> reservation known to the block (ballots, barrier; MTX_SHADE_DEFER=0: + the atomic's round trip + barrier)",
-        "-> cache-query append, next step's queue entry and hit",
-        "-> queue / shadow stores issued (deferred: the previous step's flush from LDS)",
-        "-> deferred only: second barrier, LDS stage writes, reservation atomic issued"]
+        "-> reservation known to the block (ballots, barrier, the atomic's round trip, barrier)",
+        "-> queue / shadow stores issued",
+        "-> cache-query append, next step's queue entry and hit"]
 NSEG = len(SEGS)
 
 
