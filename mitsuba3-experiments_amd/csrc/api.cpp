@@ -171,6 +171,7 @@ struct mtx_ctx {
   uint32_t occ_lds_stack = mtxd::kOccLdsStack;
   uint32_t trace_batch = 128;  // queue entries per claim (256: +0.6 % closest, +1 % at spp 32; 64: +5 %)
   uint32_t urefill = 24;  // refill a wave once 24 lanes are idle (16: closest +1.3 %, 32: +2 %; 4-wide BVH)
+  uint32_t cam_urefill = 64;  // k_trace_camera (MTX_CAM_UREFILL): whole waves refill; a refill derives its camera rays
   uint32_t occ_urefill = 12;  // any hit on the 8-wide tree (MTX_OCC_UREFILL; 8-16 alike, 24: shadow +1 ms, 32/40: +2/+3 ms)
   uint32_t xcd_claim = 1;
   // ReSTIR GI: a band of at most this many paths runs its stage A in the
@@ -257,6 +258,7 @@ int mtx_ctx_create(int hip_device, mtx_ctx **out) {
   if (const char *e = getenv("MTX_STREAMS")) c->streams = (uint32_t)std::max(1, std::min(2, atoi(e)));
   if (const char *e = getenv("MTX_TRACE_BATCH")) c->trace_batch = (uint32_t)std::max(1, std::min(1 << 16, atoi(e)));
   if (const char *e = getenv("MTX_UREFILL")) c->urefill = (uint32_t)std::max(1, std::min(64, atoi(e)));
+  if (const char *e = getenv("MTX_CAM_UREFILL")) c->cam_urefill = (uint32_t)std::max(1, std::min(64, atoi(e)));
   if (const char *e = getenv("MTX_OCC_UREFILL")) c->occ_urefill = (uint32_t)std::max(1, std::min(64, atoi(e)));
   if (const char *e = getenv("MTX_XCD_CLAIM")) c->xcd_claim = atoi(e) != 0;
   if (const char *e = getenv("MTX_RS_FUSED")) c->rs_fused = atoi(e) ? 1u : 0u;
@@ -724,6 +726,7 @@ int mtx_scene_upload(mtx_ctx *c, const mtx_scene_desc *d) {
   s.occ_lds_top = std::min<uint32_t>(n_occ, c->occ_lds_top);
   s.trace_batch = c->trace_batch;
   s.urefill = c->urefill;
+  s.cam_urefill = c->cam_urefill;
   s.occ_urefill = c->occ_urefill;
   s.xcd_claim = c->xcd_claim;
   c->trace_grid = c->n_cu * mtxd::trace_blocks_per_cu(s);
@@ -1094,7 +1097,10 @@ void launch_bounce(mtx_ctx *c, const mtxd::WaveBuffers &b, const mtxd::ChunkPara
   const int div = (nerad && bounce >= 2) ? 8 : 1;
   if (!(nerad && bounce == 0)) {
     e = tm.begin(0, st);
-    mtxd::launch_trace_closest(s, b, bounce, p.stats, std::max(1, c->closest_grid / div), st);
+    if (bounce == 0 && p.cam0)  // no stored raygen: the traversal derives its camera rays
+      mtxd::launch_trace_camera(s, b, p, std::max(1, c->closest_grid / div), st);
+    else
+      mtxd::launch_trace_closest(s, b, bounce, p.stats, std::max(1, c->closest_grid / div), st);
     tm.end(0, e, st);
     ++*n_trace;
   }
@@ -1595,6 +1601,10 @@ int mtx_render(mtx_ctx *c, const mtx_render_args *a, float *film_rgbw, int film_
     // ReSTIR's k_rs_collect build their own ChunkParams, which keep it)
     p.drop_end_misc = mlt ? 0u : 1u;
     p.ident0 = 1;  // raygen_camera / mlt_begin queue every path at its own position
+    // path, path-mis, nrc and simple derive the camera sample where it is used
+    // (no raygen launch, no bounce-0 planes, no pos). The nerad render keeps the
+    // stored raygen: its bounce-0 shade reads the raygen's misc plane by path.
+    p.cam0 = (!mlt && !nerad_render) ? MTX_CAM0 : 0u;
     if (mlt) {
       // Pssmlt.render (pssmlt.py:167-228): all iterations of this chunk's chains
       const uint32_t iters = a->iterations ? a->iterations : 200;
@@ -1611,7 +1621,10 @@ int mtx_render(mtx_ctx *c, const mtx_render_args *a, float *film_rgbw, int film_
     }
     HIP_TRY(reset_counters(bc, std::max<uint32_t>(a->max_depth, 1), st));
     if (nrc_cache || nerad_render) HIP_TRY(hipMemsetAsync(bc.cq_count, 0, 4, st));
-    mtxd::launch_raygen_camera(sc, bc, p, st);
+    if (p.cam0)  // what raygen's thread 0 did: the bounce-0 queue holds every path
+      HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)bc.counters, (int)p.n_paths, 1, st));
+    else
+      mtxd::launch_raygen_camera(sc, bc, p, st);
     run_bounces(c, bc, p, tm, &n_trace, &n_shadow, &sc, st);
     if (nrc_cache) {
       if (second)

@@ -5,7 +5,9 @@
 // nrc.py:25-125) with explicit kernels over SoA state in HBM:
 //
 //   raygen   camera rays for a chunk of (pixel, sample) lanes
-//            (transcribed render_sample, path.py:27-101)
+//            (transcribed render_sample, path.py:27-101); mtx_render's film
+//            chunks store none: the bounce-0 trace and shade and the film
+//            derive the camera sample (camera_path, ChunkParams::cam0)
 //   trace    persistent closest-hit BVH2 traversal, LDS stack per lane,
 //            rays fetched 64 at a time per wave from an atomic counter
 //            (Scene.ray_intersect, path-mis.py:69-71)
@@ -191,8 +193,8 @@ __global__ __launch_bounds__(kTraceBlock) MTX_TRACE_ATTR void k_trace_shadow(Dev
 // ---------------------------------------------------------------------------
 // Ray generation
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void init_path(const WaveBuffers &b, const ChunkParams &p, uint32_t i, const Ray &ray,
-                                          const Pcg32 &rng, float2 pos, bool env) {
+// A path's initial depth | flags << 16 word (misc.w).
+__device__ __forceinline__ uint32_t init_word(const ChunkParams &p, bool env) {
   uint32_t depth = 0, flags = 0;
   if (p.integrator == MTX_INT_PATH_MIS) {
     depth = 0;
@@ -203,12 +205,68 @@ __device__ __forceinline__ void init_path(const WaveBuffers &b, const ChunkParam
   } else {
     depth = 1;  // path.py:230, nrc.py:39
   }
+  return depth | (flags << 16);
+}
+
+// The camera sample of a chunk: everything k_raygen_camera stores for a path
+// is a function of the path's index, ChunkParams and the camera. The stored
+// form (k_raygen_camera) and the derived form (ChunkParams::cam0: CameraSrc,
+// the bounce-0 shades, the film source kernels) both come from these two
+// helpers, so they cannot drift.
+// Film position of sample `smp` of film pixel pix = (x, y); returns the
+// sampler after the two jitter draws (path.py:45).
+__device__ __forceinline__ Pcg32 camera_film_pos(const ChunkParams &p, uint32_t pix, uint32_t x, uint32_t y,
+                                                 uint32_t smp, float2 &pos) {
+  const uint32_t lane = pix * p.spp_total + p.sample_offset + smp;
+  Pcg32 rng = sampler_lane(p.seed, lane);
+  const V2 u = rng.next_2d();  // film jitter (path.py:45)
+  pos = make_float2((float)x + u.x, (float)y + u.y);
+  return rng;
+}
+struct CamPath {
+  Ray ray;
+  float2 pos;     // film position (sx, sy)
+  Pcg32 rng;      // after the jitter draws
+  uint32_t word;  // depth | flags << 16
+};
+// Path i of the chunk (pixel-major: the samples of one pixel share a wave,
+// coherent traversal).
+__device__ __forceinline__ CamPath camera_path(const mtx_camera &cam, bool env, const ChunkParams &p, uint32_t i) {
+  const uint32_t px_local = i / p.spp, smp = i - px_local * p.spp;
+  const uint32_t pix = p.px0 + px_local;
+  const uint32_t y = pix / p.width, x = pix - y * p.width;
+  CamPath cp;
+  cp.rng = camera_film_pos(p, pix, x, y, smp, cp.pos);
+  const V2 adj = V2{cp.pos.x / (float)p.width, cp.pos.y / (float)p.height};
+  cp.ray = camera_ray(cam, adj);  // path.py:60-62
+  cp.word = init_word(p, env);
+  return cp;
+}
+
+// The records init_path would have stored for camera path i (ray_o, ray_d,
+// misc), for the bounce-0 shade of a cam0 chunk (k_shade_cam).
+struct CamState {
+  float4 ro, rd;
+  uint4 mi;
+};
+__device__ __forceinline__ CamState cam_state(const DevScene &s, const ChunkParams &p, uint32_t i) {
+  const CamPath cp = camera_path(s.camera, s.has_env != 0, p, i);
+  CamState c;
+  c.ro = make_float4(cp.ray.o.x, cp.ray.o.y, cp.ray.o.z, cp.ray.maxt);
+  c.rd = make_float4(cp.ray.d.x, cp.ray.d.y, cp.ray.d.z, 0.f);
+  c.mi = make_uint4((uint32_t)cp.rng.state, (uint32_t)(cp.rng.state >> 32), cp.rng.seq, cp.word);
+  return c;
+}
+
+__device__ __forceinline__ void init_path(const WaveBuffers &b, const ChunkParams &p, uint32_t i, const Ray &ray,
+                                          const Pcg32 &rng, float2 pos, bool env) {
+  const uint32_t word = init_word(p, env);
   // throughput = 1, eta = 1, L = 0, prev_bsdf_pdf = 1 (path-mis.py:45), prev_p = 0 are
   // not stored: the bounce-0 shade uses these constants (kInitThr / kInitL / kInitPrev)
   st_stream<kNtRaygen>(b.ray_o[0] + i, make_float4(ray.o.x, ray.o.y, ray.o.z, ray.maxt));  // queue position i (identity)
   st_stream<kNtRaygen>(b.ray_d[0] + i, make_float4(ray.d.x, ray.d.y, ray.d.z, 0.f));
   st_stream<kNtRaygen>(b.misc[0] + i,
-                       make_uint4((uint32_t)rng.state, (uint32_t)(rng.state >> 32), rng.seq, depth | (flags << 16)));
+                       make_uint4((uint32_t)rng.state, (uint32_t)(rng.state >> 32), rng.seq, word));
   b.pos[i] = pos;
   if (!p.ident0) b.queue[0][i] = i;
 }
@@ -217,18 +275,49 @@ __global__ void k_raygen_camera(DevScene s, WaveBuffers b, ChunkParams p) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i == 0) b.counters[0] = p.n_paths;
   if (i >= p.n_paths) return;
-  // path order within the chunk: pixel-major keeps the samples of one pixel
-  // in one wave (coherent traversal)
-  const uint32_t px_local = i / p.spp, smp = i - px_local * p.spp;
-  const uint32_t pix = p.px0 + px_local;
-  const uint32_t y = pix / p.width, x = pix - y * p.width;
-  const uint32_t lane = pix * p.spp_total + p.sample_offset + smp;
-  Pcg32 rng = sampler_lane(p.seed, lane);
-  const V2 u = rng.next_2d();  // film jitter (path.py:45)
-  const float sx = (float)x + u.x, sy = (float)y + u.y;
-  const V2 adj = V2{sx / (float)p.width, sy / (float)p.height};
-  const Ray ray = camera_ray(s.camera, adj);  // path.py:60-62
-  init_path(b, p, i, ray, rng, make_float2(sx, sy), s.has_env != 0);
+  const CamPath cp = camera_path(s.camera, s.has_env != 0, p, i);
+  init_path(b, p, i, cp.ray, cp.rng, cp.pos, s.has_env != 0);
+}
+
+// Bounce-0 closest hit of a camera chunk without stored rays (ChunkParams::
+// cam0): the ray of queue position k (= path k, the identity queue) is derived
+// where the traversal takes it; the hit record goes where ClosestSrc puts it.
+struct CameraSrc {
+  using Payload = uint32_t;  // the queue position
+  const DevScene &s;
+  const WaveBuffers &b;
+  const ChunkParams &p;
+  __device__ __forceinline__ void load(uint32_t k, TraceRay &r, float &tmax, uint32_t &payload) const {
+    const CamPath cp = camera_path(s.camera, s.has_env != 0, p, k);
+    r = make_trace_ray(cp.ray.o, cp.ray.d, cp.ray.maxt);
+    tmax = cp.ray.maxt;
+    payload = k;
+  }
+  __device__ __forceinline__ void finish(uint32_t slot, bool, float t, uint32_t prim, float u, float v) const {
+    st_stream<kNtTraceSt>(b.hit + slot, make_float4(prim == 0xffffffffu ? kInf : t, __uint_as_float(prim), u, v));
+  }
+};
+
+// Its own kernel: k_trace_closest keeps its code and registers. Launched with
+// the refill threshold DevScene::cam_urefill (launch_trace_camera): load() is
+// ~300 VALU instructions, run for the refilling lanes only.
+template <bool STATS>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MTX_CLOSEST_WAVES))) void k_trace_camera(DevScene s, WaveBuffers b, ChunkParams p) {
+  // dynamic LDS: stack columns + tree top (device_common.h trace_loop)
+  const CameraSrc src{s, b, p};
+  uint32_t nv = 0, tv = 0, nr = 0, wi[2] = {0, 0};
+  trace_loop<false, STATS>(s, src, p.n_paths, b.xheads, nv, tv, nr, wi);
+  if (STATS) {
+    unsigned long long a = wave_sum_u64(nv), c = wave_sum_u64(tv), n = wave_sum_u64(nr);
+    unsigned long long w0 = wave_sum_u64(wi[0]), w1 = wave_sum_u64(wi[1]);
+    if ((threadIdx.x & 63) == 0 && n) {
+      atomicAdd(&b.stats[0], a);
+      atomicAdd(&b.stats[1], c);
+      atomicAdd(&b.stats[4], n);
+      atomicAdd(&b.stats[6], w0);
+      atomicAdd(&b.stats[7], w1);
+    }
+  }
 }
 
 __global__ void k_raygen_rays(DevScene s, WaveBuffers b, ChunkParams p, const float *rays, const uint32_t *lanes,
@@ -412,12 +501,26 @@ __device__ __forceinline__ bool end_valid(const WaveBuffers &b, uint32_t path, f
   (void)path;
   return lw != 0.f;
 }
-template <int INT>
+// CAM: bounce 0 of a cam0 chunk (k_shade_cam; bounce_ is 0): no stored
+// raygen, the camera ray and the sampler state of path `path` are derived.
+template <int INT, bool CAM = false>
 __device__ __forceinline__ bool shade_path(const DevScene &s, const SceneView &sv, const WaveBuffers &b,
-                                           const ChunkParams &p, uint32_t bounce, uint32_t path, uint32_t qi,
+                                           const ChunkParams &p, uint32_t bounce_, uint32_t path, uint32_t qi,
                                            const float4 h, ShadeIO &io, const float4 *warm = nullptr) {
+  const uint32_t bounce = CAM ? 0u : bounce_;
   const uint32_t rp = (bounce + b.ray_par) & 1u;
-  const float4 ro = ld_stream<kNtShade>(b.ray_o[rp] + qi), rd = ld_stream<kNtShade>(b.ray_d[rp] + qi);
+  float4 ro, rd;
+  uint4 mi;
+  constexpr bool cam = CAM;
+  if constexpr (CAM) {
+    const CamState c = cam_state(s, p, path);
+    ro = c.ro;
+    rd = c.rd;
+    mi = c.mi;
+  } else {
+    ro = ld_stream<kNtShade>(b.ray_o[rp] + qi);
+    rd = ld_stream<kNtShade>(b.ray_d[rp] + qi);
+  }
   // bounce 0: the state init_path / k_rs_begin would have stored (not read)
   const float4 th = bounce == 0 ? kInitThr : ld_stream<kNtShade>(b.thr[rp] + qi),
                Lr = bounce == 0 ? kInitL : ld_stream<kNtShade>(b.L[rp] + qi);
@@ -427,7 +530,7 @@ __device__ __forceinline__ bool shade_path(const DevScene &s, const SceneView &s
   constexpr bool kPrevOnEmitter = INT == MTX_INT_PATH_MIS || INT == MTX_INT_PATH;
   float4 pv = kInitPrev;
   if (!kPrevOnEmitter && bounce != 0) pv = ld_stream<kNtShade>(b.prev[rp] + qi);
-  const uint4 mi = ld_stream<kNtShade>(b.misc[rp] + qi);
+  if (!cam) mi = ld_stream<kNtShade>(b.misc[rp] + qi);
   io.nL = Lr;  // an exit that changes neither keeps them
   io.nmisc = mi;
   Pcg32 rng;
@@ -711,13 +814,23 @@ __device__ __forceinline__ bool shade_pssmlt(const DevScene &s, const SceneView 
 // (:104-111). 4 draws per executed bounce. The same loop as
 // pssmltsimple.py:60-131 without the mutation; bounce 0 starts from the
 // constant initial state (f = 1, eta = 1, L = 0, prev_bsdf_pdf = 1).
+template <bool CAM = false>  // CAM: bounce 0 of a cam0 chunk, as in shade_path
 __device__ __forceinline__ bool shade_simple(const DevScene &s, const SceneView &sv, const WaveBuffers &b,
-                                             const ChunkParams &p, uint32_t bounce, uint32_t path, uint32_t qi,
+                                             const ChunkParams &p, uint32_t bounce_, uint32_t path, uint32_t qi,
                                              const float4 h, ShadeIO &io) {
+  const uint32_t bounce = CAM ? 0u : bounce_;
   const uint32_t rp = (bounce + b.ray_par) & 1u;
-  const float4 rd = b.ray_d[rp][qi];
+  float4 rd;
+  uint4 mi;
+  if constexpr (CAM) {
+    const CamState c = cam_state(s, p, path);
+    rd = c.rd;
+    mi = c.mi;
+  } else {
+    rd = b.ray_d[rp][qi];
+    mi = b.misc[rp][qi];
+  }
   const float4 th = bounce == 0 ? kInitThr : b.thr[rp][qi], Lr = bounce == 0 ? kInitL : b.L[rp][qi];
-  const uint4 mi = b.misc[rp][qi];
   Pcg32 rng;
   rng.state = ((uint64_t)mi.y << 32) | (uint64_t)mi.x;
   rng.seq = mi.z;
@@ -983,8 +1096,12 @@ __device__ __forceinline__ bool shade_nerad(const DevScene &s, const SceneView &
 // blocks per CU the shade kernels are built for (their register budget):
 // kShadeMinBlocks for every integrator (pssmltpath.py's shade at 2 blocks,
 // without its spills, measured slower: DESIGN.md §7)
-template <int INT>
-__global__ __launch_bounds__(kShadeBlock, kShadeMinBlocks) void k_shade(DevScene s, WaveBuffers b, ChunkParams p, uint32_t bounce) {
+// The persistent shade loop of a bounce: k_shade's body. CAM: bounce 0 of a
+// cam0 chunk (k_shade_cam), bounce_ is 0.
+template <int INT, bool CAM>
+__device__ __forceinline__ void shade_loop(const DevScene &s, const WaveBuffers &b, const ChunkParams &p,
+                                           uint32_t bounce_) {
+  const uint32_t bounce = CAM ? 0u : bounce_;
   const SceneView sv = make_view(s);
   const uint32_t count = b.counters[4 * bounce + 0];
   const uint32_t *in_q = b.queue[bounce & 1];
@@ -1037,7 +1154,7 @@ __global__ __launch_bounds__(kShadeBlock, kShadeMinBlocks) void k_shade(DevScene
       if constexpr (INT == MTX_INT_PSSMLT_SIMPLE)
         cont = shade_pssmlt(s, sv, b, p, bounce, path, i, h, io);
       else if constexpr (INT == MTX_INT_SIMPLE)
-        cont = shade_simple(s, sv, b, p, bounce, path, i, h, io);
+        cont = shade_simple<CAM>(s, sv, b, p, bounce, path, i, h, io);
       else if constexpr (INT == MTX_INT_PSSMLT_PATH)
         cont = shade_pssmlt_path(s, sv, b, p, bounce, path, i, h, io);
       else if constexpr (INT == MTX_INT_NERAD_RHS)
@@ -1045,7 +1162,7 @@ __global__ __launch_bounds__(kShadeBlock, kShadeMinBlocks) void k_shade(DevScene
       else if constexpr (INT == MTX_INT_NERAD)
         cont = shade_nerad<true>(s, sv, b, bounce, path, i, h, io);
       else
-        cont = shade_path<INT>(s, sv, b, p, bounce, path, i, h, io, wp);
+        cont = shade_path<INT, CAM>(s, sv, b, p, bounce, path, i, h, io, wp);
     }
     (void)wp;
     const uint32_t path_c = path;
@@ -1105,6 +1222,22 @@ __global__ __launch_bounds__(kShadeBlock, kShadeMinBlocks) void k_shade(DevScene
     atomicAdd(&g_shade_stamps[kStampSegs + 1], 1ull);
   }
 #endif
+}
+
+template <int INT>
+__global__ __launch_bounds__(kShadeBlock, kShadeMinBlocks) void k_shade(DevScene s, WaveBuffers b, ChunkParams p, uint32_t bounce) {
+  shade_loop<INT, false>(s, b, p, bounce);
+}
+// Bounce 0 of a cam0 chunk (path, path-mis, nrc, simple): the camera sample
+// is derived, not loaded. Its own kernel: k_shade keeps its code and
+// registers (in one kernel the camera's and the chunk's scalars stay live
+// through every bounce's loop, and k_shade<NRC>, at its 168-VGPR budget,
+// spills), and bounce == 0 is a constant here (no state loads at all).
+template <int INT>
+__global__ __launch_bounds__(kShadeBlock, kShadeMinBlocks) void k_shade_cam(DevScene s, WaveBuffers b, ChunkParams p) {
+  static_assert(INT == MTX_INT_PATH || INT == MTX_INT_PATH_MIS || INT == MTX_INT_NRC || INT == MTX_INT_SIMPLE,
+                "k_shade_cam: the integrators whose bounce-0 shade derives the camera sample");
+  shade_loop<INT, true>(s, b, p, 0u);
 }
 
 // Paths still queued after a chunk's last bounce (its depth limit stops
@@ -1511,20 +1644,27 @@ __global__ __launch_bounds__(64) void k_film_src_staged(WaveBuffers b, ChunkPara
         const uint32_t path = (q0 + j) * p.spp + s0 + sm;
         float4 l = ld_stream<kNtQueue>(b.L[kFinal] + path);
         if (mask_valid && !end_valid(b, path, l.w)) l = make_float4(0.f, 0.f, 0.f, 0.f);
-        const float2 ps = ld_stream<kNtQueue>(b.pos + path);
         sv[0][j][sm] = l.x;
         sv[1][j][sm] = l.y;
         sv[2][j][sm] = l.z;
-        sv[3][j][sm] = ps.x;
-        sv[4][j][sm] = ps.y;
+        if (!p.cam0) {
+          const float2 ps = ld_stream<kNtQueue>(b.pos + path);
+          sv[3][j][sm] = ps.x;
+          sv[4][j][sm] = ps.y;
+        }
       }
     }
     __syncthreads();
     for (uint32_t sm = 0; sm < ns; ++sm) {
       fs.advance(p.sample_offset + s0 + sm, acc, contrib, p, o, live);
-      if (live)
-        film_accumulate<N, F>(acc, x, y, make_float2(sv[3][lane][sm], sv[4][lane][sm]),
-                              V3{sv[0][lane][sm], sv[1][lane][sm], sv[2][lane][sm]});
+      if (live) {
+        float2 ps;
+        if (p.cam0)  // no stored raygen: the sample's film position is derived
+          camera_film_pos(p, pix, (uint32_t)x, (uint32_t)y, s0 + sm, ps);
+        else
+          ps = make_float2(sv[3][lane][sm], sv[4][lane][sm]);
+        film_accumulate<N, F>(acc, x, y, ps, V3{sv[0][lane][sm], sv[1][lane][sm], sv[2][lane][sm]});
+      }
     }
     __syncthreads();
   }
@@ -1548,7 +1688,12 @@ __global__ __launch_bounds__(film_max_block(N)) void k_film_src(WaveBuffers b, C
   for (uint32_t sidx = 0; sidx < p.spp; ++sidx) {
     fs.advance(p.sample_offset + sidx, acc, contrib, p, o, true);
     const uint32_t path = q * p.spp + sidx;
-    film_accumulate<N, F>(acc, x, y, b.pos[path], final_L(b, p, path));
+    float2 ps;
+    if (p.cam0)  // no stored raygen: the sample's film position is derived
+      camera_film_pos(p, pix, (uint32_t)x, (uint32_t)y, sidx, ps);
+    else
+      ps = b.pos[path];
+    film_accumulate<N, F>(acc, x, y, ps, final_L(b, p, path));
   }
   fs.finish(acc, contrib, p, o);
 }
@@ -1789,6 +1934,15 @@ void launch_trace_closest(const DevScene &s, const WaveBuffers &b, uint32_t boun
   else
     hipLaunchKernelGGL(k_trace_closest<false>, dim3(grid), dim3(kTraceBlock), lds, st, s, b, bounce);
 }
+void launch_trace_camera(const DevScene &scene, const WaveBuffers &b, const ChunkParams &p, int grid, hipStream_t st) {
+  DevScene s = scene;
+  s.urefill = scene.cam_urefill;  // the traversal's refill threshold, for this kernel
+  const size_t lds = persistent_stack_bytes(s, false);
+  if (p.stats)
+    hipLaunchKernelGGL(k_trace_camera<true>, dim3(grid), dim3(kTraceBlock), lds, st, s, b, p);
+  else
+    hipLaunchKernelGGL(k_trace_camera<false>, dim3(grid), dim3(kTraceBlock), lds, st, s, b, p);
+}
 void launch_trace_shadow(const DevScene &s, const WaveBuffers &b, uint32_t bounce, uint32_t stats, int grid,
                          hipStream_t st) {
   if (stats)
@@ -1798,6 +1952,22 @@ void launch_trace_shadow(const DevScene &s, const WaveBuffers &b, uint32_t bounc
 }
 void launch_shade(const DevScene &s, const WaveBuffers &b, const ChunkParams &p, uint32_t bounce, int grid,
                   hipStream_t st) {
+  if (bounce == 0 && p.cam0) {  // no stored raygen (mtx_render sets cam0 for these four only)
+    switch (p.integrator) {
+      case MTX_INT_PATH:
+        hipLaunchKernelGGL(k_shade_cam<MTX_INT_PATH>, dim3(grid), dim3(kShadeBlock), 0, st, s, b, p);
+        break;
+      case MTX_INT_NRC:
+        hipLaunchKernelGGL(k_shade_cam<MTX_INT_NRC>, dim3(grid), dim3(kShadeBlock), 0, st, s, b, p);
+        break;
+      case MTX_INT_SIMPLE:
+        hipLaunchKernelGGL(k_shade_cam<MTX_INT_SIMPLE>, dim3(grid), dim3(kShadeBlock), 0, st, s, b, p);
+        break;
+      default:
+        hipLaunchKernelGGL(k_shade_cam<MTX_INT_PATH_MIS>, dim3(grid), dim3(kShadeBlock), 0, st, s, b, p);
+    }
+    return;
+  }
   switch (p.integrator) {
     case MTX_INT_PATH:
       hipLaunchKernelGGL(k_shade<MTX_INT_PATH>, dim3(grid), dim3(kShadeBlock), 0, st, s, b, p, bounce);

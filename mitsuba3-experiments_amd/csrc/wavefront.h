@@ -18,6 +18,9 @@
 // plane that an ending path's state lands in (film, chain and ReSTIR
 // kernels). pos is per path, hit per queue position. Paths of a chunk are
 // pixel-major: path = q * spp + s for sample s of the chunk's pixel q.
+// A cam0 chunk (ChunkParams: the film renders of path, path-mis, nrc and
+// simple) has no raygen, so no bounce-0 ray_o / ray_d / misc and no pos: the
+// camera sample is derived from the path index where it is used.
 // Queues are u32 path indices compacted per 256-thread block (ballot + mbcnt
 // + LDS, one atomic per block step); shadow rays are four planes of 16-byte
 // word groups, indexed by their own queue position.
@@ -60,6 +63,9 @@ constexpr uint32_t kOccLdsStack = 8;
 #ifndef MTX_ENCODE_LM
 #define MTX_ENCODE_LM 1  // NRC cache encoder with level-major lanes (field.hip k_field_encode_lm)
 #endif
+#ifndef MTX_CAM0
+#define MTX_CAM0 1  // mtx_render: camera chunks derive their rays (ChunkParams::cam0; 0 = stored raygen, A/B)
+#endif
 #ifndef MTX_STREAMS
 #define MTX_STREAMS 2  // mtx_render: chunks alternate between two wavefronts on two streams (1 = one)
 #endif
@@ -98,6 +104,7 @@ struct DevScene {
                            // (int32 node refs for closest hit, uint2 node groups for occlusion)
   uint32_t ovf_threads;    // threads of the persistent trace grid
   uint32_t urefill;        // persistent kernels: refill a wave once this many lanes are idle
+  uint32_t cam_urefill;    // the same for k_trace_camera, whose refill derives the rays
   uint32_t occ_urefill;    // the same for the any-hit kernels
   uint32_t xcd_claim;      // persistent kernels: claim rays from the own XCD's queue segment first
   mtx_camera camera;
@@ -147,8 +154,8 @@ struct WaveBuffers {
   // a shadow record addresses its target as plane * capacity + index.
   float4 *L[3];
   uint4 *misc[3];
-  float2 *pos;
-  float4 *hit;
+  float2 *pos;          // film position by path; neither written nor read under ChunkParams::cam0
+  float4 *hit;          // this bounce's hit records, by queue position
   uint32_t *queue[2];
   float4 *shadow;       // four planes of `capacity` word groups: o | d | t | x (above)
   uint32_t *counters;   // per bounce b: [4b+0] rays of bounce b, [4b+1] shadow rays of bounce b-1 (one 8-B pair with the queue shade b-1 fills), [4b+2], [4b+3] unused
@@ -221,6 +228,9 @@ struct ChunkParams {
   uint32_t nrc_cache;     // NRC: query the radiance field where the spread criterion stops
   uint32_t drop_end_misc; // film render: an ending path's sampler state is never read (its L is)
   uint32_t ident0;        // the bounce-0 queue is the identity (raygen): not stored, k_shade uses position = path
+  uint32_t cam0;          // camera chunk without a stored raygen (needs ident0): the bounce-0 planes of ray_o /
+                          // ray_d / misc and pos do not exist; the bounce-0 closest hit (k_trace_camera), the
+                          // bounce-0 shade and the film source kernels derive them (kernels.hip camera_path)
 };
 
 // -------- launch wrappers (kernels.hip) --------
@@ -239,6 +249,8 @@ void launch_raygen_rays(const DevScene &s, const WaveBuffers &b, const ChunkPara
                         const uint32_t *lanes, uint32_t rng_skip, hipStream_t st);
 void launch_trace_closest(const DevScene &s, const WaveBuffers &b, uint32_t bounce, uint32_t stats, int grid,
                           hipStream_t st);
+// bounce-0 closest hit of a cam0 chunk: camera rays derived in the traversal (kernels.hip CameraSrc)
+void launch_trace_camera(const DevScene &s, const WaveBuffers &b, const ChunkParams &p, int grid, hipStream_t st);
 void launch_trace_shadow(const DevScene &s, const WaveBuffers &b, uint32_t bounce, uint32_t stats, int grid,
                          hipStream_t st);
 void launch_shade(const DevScene &s, const WaveBuffers &b, const ChunkParams &p, uint32_t bounce, int grid,
