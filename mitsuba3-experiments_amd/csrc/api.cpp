@@ -46,9 +46,17 @@ void mtx_set_error(const char *fmt, ...) {
 
 namespace {
 
+// A device allocation and its owner: freed with the object that holds it
+// (mtx_ctx_destroy frees every buffer of a context by deleting the context).
 struct DevBuf {
   void *p = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() {
+    if (p) hipFree(p);
+  }
 };
 
 int dalloc(DevBuf &b, size_t bytes) {
@@ -87,34 +95,60 @@ int upload(DevBuf &b, const T *src, size_t count, hipStream_t st) {
 
 }  // namespace
 
-// Second wavefront of the two-stream render (mtx_render's path / path-mis /
-// nrc / simple integrators): its own path state, queues, counters, claim
-// cursors and traversal spill area, on its own stream. The film's chunks
-// alternate between the two wavefronts, so one chunk's kernels fill the
-// GPU while the other's persistent trace launches drain their tails.
-struct Wave2 {
+// The per-path planes of a wavefront (wavefront.h WaveBuffers): `sub`
+// sub-planes of `elem`-byte entries, one wavefront capacity apart. The one
+// statement of the layout: ensure_wave sizes a plane from it and plane_at
+// places a sub-plane by it.
+enum PlaneId { kRayO, kRayD, kThr, kL, kPrev, kMisc, kPos, kHit, kQ0, kQ1, kShadow, kNumPlanes };
+struct PlaneDesc {
+  uint32_t elem, sub;
+};
+constexpr PlaneDesc kPlanes[kNumPlanes] = {
+    {16, 2},  // ray_o: bounce parity
+    {16, 2},  // ray_d
+    {16, 2},  // thr
+    {16, 3},  // L: queue planes 0 / 1 + the per-path plane
+    {16, 2},  // prev
+    {16, 3},  // misc
+    {8, 1},   // pos
+    {16, 1},  // hit
+    {4, 1},   // queue 0
+    {4, 1},   // queue 1
+    {16, 4},  // shadow: four planes of 16-B word groups
+};
+
+// One wavefront: its path state, queues, shadow records, counters and claim
+// cursors, its traversal spill area, its NRC cache-query buffers and the
+// stream its kernels run on. Wave 0 runs on the context's stream. Wave 1 is
+// the second wavefront of a two-stream render (mtx_render's path / path-mis /
+// nrc / simple integrators, ReSTIR GI's stage A): the film's chunks alternate
+// between the two, so one chunk's kernels fill the GPU while the other's
+// persistent trace launches drain their tails. Its stream and events are
+// created by its first ensure_wave.
+struct Wave {
   hipStream_t stream = nullptr;
-  hipEvent_t start = nullptr, done = nullptr;
-  DevBuf ray_o, ray_d, thr, L, prev, misc, pos, hit, q0, q1, shadow, counters, xheads, stack_ovf, cq_perm, cq_cursor;
-  DevBuf cq_p, cq_d, cq_t, cq_count, f_feat, f_out;  // NRC radiance-cache queries of its chunks
+  hipEvent_t start = nullptr, done = nullptr;  // wave 1: fork from / join into wave 0's stream
+  DevBuf plane[kNumPlanes];
+  DevBuf counters, xheads;  // queue counters, per-XCD claim cursors of the persistent trace kernels
+  DevBuf stack_ovf;         // traversal stack entries beyond the LDS part (two waves' traces may run at once)
+  DevBuf cq_p, cq_d, cq_t, cq_count, f_feat, f_out;  // NRC cache queries of a chunk, their features and outputs
+  DevBuf cq_perm, cq_cursor;  // region-grouped query order (the Morton sort keeps its keys in cq_cursor)
   uint32_t capacity = 0;
 };
 
 struct mtx_ctx {
   int device = 0;
   int n_cu = 256;
-  hipStream_t stream = nullptr;
-  Wave2 w2;
+  hipStream_t stream = nullptr;  // wave[0].stream is the same handle
+  Wave wave[2];
   uint32_t *q_pinned = nullptr;  // per-chunk cache-query counts of a stats render (pinned, kQSlots)
   uint32_t streams = MTX_STREAMS;  // 1: every chunk on `stream` (MTX_STREAMS env: A/B)
   uint32_t streams_max_log2 = 27;  // two streams for renders of <= 2^this paths (MTX_STREAMS_MAX_LOG2: A/B)
   bool has_scene = false;
   // scene
-  DevBuf stack_ovf;  // traversal stack entries beyond the LDS part
   DevBuf shade_rec;  // per-triangle shading records
   // radiance field (mtx_field_upload)
-  DevBuf field_table, field_frag, fq_p, fq_d, f_feat, f_out;
-  DevBuf cq_p, cq_d, cq_t, cq_count;  // NRC cache queries of a chunk
+  DevBuf field_table, field_frag, fq_p, fq_d;
   mtx::FieldEncoding field{};
   uint32_t field_hidden = 0;
   bool has_field = false;
@@ -145,10 +179,9 @@ struct mtx_ctx {
   DevBuf occ_perm, lvl4_list, lvl8_list, rf_state, rf_tbox, rf_nbox, rf_vpos, rf_vnormal;
   std::vector<uint32_t> lvl4_first, lvl8_first;
   uint32_t scene_n_nodes = 0, scene_n_occ = 0, scene_n_verts = 0;
-  // wavefront
-  DevBuf ray_o, ray_d, thr, L, prev, misc, pos, hit, q0, q1, shadow, counters, stats;
-  DevBuf xheads, rs_heads;  // per-XCD claim cursors of the persistent trace kernels
-  uint32_t capacity = 0;
+  // shared by both wavefronts
+  DevBuf stats;
+  DevBuf rs_heads;  // per-XCD claim cursors of k_trace_test
   DevBuf mlt_cur, mlt_L, mlt_prop, vpath, vprop;  // PSSMLT chain state
   DevBuf vpath_es, vprop_es;                       // pssmltpath emitter samples
   uint32_t mlt_capacity = 0, mlt_depth = 0, mlt_es_capacity = 0, mlt_es_depth = 0;
@@ -191,7 +224,7 @@ struct mtx_ctx {
   uint32_t encode_lm = MTX_ENCODE_LM;
   // NRC cache: encode + MLP + apply in one launch (field.hip k_field_cache_fused; MTX_CACHE_FUSED=0: three)
   uint32_t cache_fused = 1;
-  DevBuf cq_keys, cq_perm, cq_ws;
+  DevBuf cq_ws;  // sort workspace of the Morton order
   std::vector<hipEvent_t> events;
   hipEvent_t prim_ev[2] = {nullptr, nullptr};
   double last_device_ms = 0.0;
@@ -236,6 +269,7 @@ int mtx_ctx_create(int hip_device, mtx_ctx **out) {
     mtx_set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
     return MTX_E_HIP;
   }
+  c->wave[0].stream = c->stream;
   // Persistent grids: every CU filled to the kernels' occupancy (the trace
   // grid is recomputed per scene: its LDS stack depends on the BVH depth).
   c->trace_grid = c->closest_grid = c->n_cu * 8;
@@ -273,39 +307,20 @@ int mtx_ctx_create(int hip_device, mtx_ctx **out) {
 void mtx_ctx_destroy(mtx_ctx *c) {
   if (!c) return;
   hipSetDevice(c->device);
-  if (c->stream) hipStreamSynchronize(c->stream);
-  if (c->w2.stream) hipStreamSynchronize(c->w2.stream);
-  DevBuf *bufs[] = {&c->nodes,  &c->tri, &c->occ_nodes, &c->occ_tri, &c->tri_vidx, &c->tri_shape, &c->vpos,     &c->vnormal, &c->vuv,
-                    &c->shapes, &c->materials, &c->emitters, &c->textures, &c->texels, &c->tables, &c->ray_o,
-                    &c->ray_d,  &c->thr,     &c->L,        &c->prev,      &c->misc,     &c->pos,     &c->hit,
-                    &c->q0,     &c->q1,      &c->shadow,   &c->counters, &c->xheads, &c->rs_heads,  &c->stats,    &c->contrib, &c->film,
-                    &c->mlt_cur, &c->mlt_L, &c->mlt_prop, &c->vpath, &c->vprop, &c->vpath_es, &c->vprop_es,
-                    &c->stack_ovf, &c->shade_rec, &c->field_table, &c->field_frag, &c->fq_p, &c->fq_d,
-                    &c->f_feat, &c->f_out, &c->cq_p, &c->cq_d, &c->cq_t, &c->cq_count, &c->rs_samp[0], &c->rs_samp[1], &c->rs_tres, &c->rs_sres, &c->rs_radius, &c->rs_hit,
-                    &c->rs_dir, &c->rs_emit, &c->rs_rng, &c->rs_rays, &c->rs_count, &c->rs_occ, &c->rs_qM, &c->rs_nbr, &c->rs_xs, &c->rs_ns,
-                    &c->s0,     &c->s1,      &c->s2,       &c->s3,        &c->s4,       &c->s5, &c->s6,
-                    &c->cq_keys, &c->cq_perm, &c->cq_ws,
-                    &c->field_w16, &c->tr_p, &c->tr_m, &c->tr_v, &c->tr_g, &c->tr_wpart, &c->tr_loss, &c->tr_out,
-                    &c->tr_dfeat, &c->tr_feat, &c->tr_flag, &c->tr_target, &c->nr_shape_pmf, &c->nr_shape_cdf,
-                    &c->nr_tri_off, &c->nr_tri_pmf, &c->nr_tri_cdf, &c->nr_tri_prim, &c->nr_dists, &c->nr_lhs,
-                    &c->nr_qp, &c->nr_qd, &c->nr_Lrhs, &c->nr_lanes,
-                    &c->occ_perm, &c->lvl4_list, &c->lvl8_list, &c->rf_state, &c->rf_tbox, &c->rf_nbox, &c->rf_vpos,
-                    &c->rf_vnormal};
-  for (DevBuf *b : bufs) dfree(*b);
-  Wave2 &w = c->w2;
-  for (DevBuf *b : {&w.ray_o, &w.ray_d, &w.thr, &w.L, &w.prev, &w.misc, &w.pos, &w.hit, &w.q0, &w.q1, &w.shadow,
-                    &w.counters, &w.xheads, &w.stack_ovf, &w.cq_p, &w.cq_d, &w.cq_t, &w.cq_count, &w.f_feat,
-                    &w.f_out, &w.cq_perm, &w.cq_cursor})
-    dfree(*b);
-  if (w.start) hipEventDestroy(w.start);
-  if (w.done) hipEventDestroy(w.done);
-  if (w.stream) hipStreamDestroy(w.stream);
+  // both streams idle before anything they use goes; wave[0].stream is
+  // c->stream and is destroyed once
+  for (Wave &w : c->wave)
+    if (w.stream) hipStreamSynchronize(w.stream);
+  Wave &w1 = c->wave[1];
+  if (w1.start) hipEventDestroy(w1.start);
+  if (w1.done) hipEventDestroy(w1.done);
+  if (w1.stream) hipStreamDestroy(w1.stream);
   for (hipEvent_t ev : c->events) hipEventDestroy(ev);
   if (c->q_pinned) hipHostFree(c->q_pinned);
   for (hipEvent_t ev : c->prim_ev)
     if (ev) hipEventDestroy(ev);
   if (c->stream) hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // every DevBuf member frees its memory (the device is still current)
 }
 
 // Caller-supplied occlusion trees: their triangle records must be the
@@ -733,8 +748,8 @@ int mtx_scene_upload(mtx_ctx *c, const mtx_scene_desc *d) {
   c->closest_grid = c->n_cu * mtxd::closest_blocks_per_cu(s);
   c->mega_grid = c->n_cu * mtxd::mega_blocks_per_cu(s);
   s.ovf_threads = (uint32_t)std::max(c->trace_grid, c->closest_grid) * mtxd::kTraceBlock;
-  if ((rc = dalloc(c->stack_ovf, mtxd::stack_ovf_bytes(s)))) return rc;
-  s.stack_ovf = c->stack_ovf.p;
+  if ((rc = dalloc(c->wave[0].stack_ovf, mtxd::stack_ovf_bytes(s)))) return rc;  // wave 1's: ensure_wave
+  s.stack_ovf = c->wave[0].stack_ovf.p;
   c->has_scene = true;
   return MTX_OK;
 }
@@ -748,7 +763,10 @@ namespace {
 // 40 % of the free HBM.
 constexpr uint32_t kDefaultChunk = 1u << 28;
 constexpr size_t kPathStateBytes = 328;
-constexpr size_t kCacheQueryBytes = 16 * 3 + 128 + 12;  // ensure_cache: query planes, features, outputs
+// per NRC cache / field query: each of the three query planes (p, d, T),
+// the fp16 feature row, the RGB output
+constexpr size_t kQueryBytes = 16, kFeatBytes = 128, kOutBytes = 12;
+constexpr size_t kCacheQueryBytes = 3 * kQueryBytes + kFeatBytes + kOutBytes;  // what ensure_cache allocates
 // `ways` wavefronts of the returned size are allocated (2 for a two-stream
 // render), each with the NRC cache-query buffers when `cache`: the budget is
 // 40 % of the free HBM for all of them together. Buffers this context already
@@ -762,56 +780,69 @@ uint32_t default_chunk(mtx_ctx *c, const mtx_render_args *a, uint32_t ways, bool
       (a->integrator == MTX_INT_PSSMLT_SIMPLE ? 32ull * std::max<uint32_t>(a->max_depth, 1) + 48
        : a->integrator == MTX_INT_PSSMLT_PATH ? 48ull * std::max<uint32_t>(a->max_depth, 1) + 48
                                               : 0);
-  const size_t held = ways > 1 ? std::min<size_t>(c->capacity, c->w2.capacity) : c->capacity;
+  const size_t held =
+      ways > 1 ? std::min<size_t>(c->wave[0].capacity, c->wave[1].capacity) : c->wave[0].capacity;
   const size_t fit = std::max<size_t>((size_t)((double)free_b * 0.4) / (per_path * std::max<uint32_t>(ways, 1)), held);
   return (uint32_t)std::max<size_t>(1u << 20, std::min<size_t>(kDefaultChunk, fit));
 }
 
-int ensure_wavefront(mtx_ctx *c, uint32_t cap, uint32_t max_depth) {
-  int rc;
-  if (cap > c->capacity) {
-    if ((rc = dalloc(c->ray_o, 32ull * cap))) return rc;  // two planes (bounce parity), wavefront.h
-    if ((rc = dalloc(c->ray_d, 32ull * cap))) return rc;
-    if ((rc = dalloc(c->thr, 32ull * cap))) return rc;
-    if ((rc = dalloc(c->L, 48ull * cap))) return rc;  // queue planes 0 / 1 + the per-path plane
+// Queue counters and per-XCD claim cursors of a render of `depth` bounces.
+constexpr size_t counters_bytes(uint32_t depth) { return 16ull * (depth + 2); }
+constexpr size_t xheads_bytes(uint32_t depth) { return 8ull * mtxd::kXSlotWords * (depth + 2); }
 
-    if ((rc = dalloc(c->prev, 32ull * cap))) return rc;
-    if ((rc = dalloc(c->misc, 48ull * cap))) return rc;
-    if ((rc = dalloc(c->pos, 8ull * cap))) return rc;
-    if ((rc = dalloc(c->hit, 16ull * cap))) return rc;
-    if ((rc = dalloc(c->q0, 4ull * cap))) return rc;
-    if ((rc = dalloc(c->q1, 4ull * cap))) return rc;
-    if ((rc = dalloc(c->shadow, 64ull * cap))) return rc;  // four planes of 16-B word groups
-    c->capacity = cap;
+// Wave `w` for `cap` paths of `max_depth` bounces. Wave 1 gets its stream
+// and events on first use, and a traversal spill area of its own (two trace
+// launches may run at once); wave 0's was sized by mtx_scene_upload for the
+// same scene, so the dalloc below leaves it alone.
+int ensure_wave(mtx_ctx *c, Wave &w, uint32_t cap, uint32_t max_depth) {
+  int rc;
+  if (!w.stream) {
+    HIP_TRY(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&w.start, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
   }
-  if ((rc = dalloc(c->counters, 16ull * (max_depth + 2)))) return rc;
-  if ((rc = dalloc(c->xheads, 8ull * mtxd::kXSlotWords * (max_depth + 2)))) return rc;
+  if (cap > w.capacity) {
+    for (int k = 0; k < kNumPlanes; ++k)
+      if ((rc = dalloc(w.plane[k], (size_t)kPlanes[k].elem * kPlanes[k].sub * cap))) return rc;
+    w.capacity = cap;
+  }
+  if ((rc = dalloc(w.counters, counters_bytes(max_depth)))) return rc;
+  if ((rc = dalloc(w.xheads, xheads_bytes(max_depth)))) return rc;
+  if ((rc = dalloc(w.stack_ovf, mtxd::stack_ovf_bytes(c->scene)))) return rc;
   if ((rc = dalloc(c->stats, 8 * 8))) return rc;
   return MTX_OK;
 }
 
-mtxd::WaveBuffers buffers(mtx_ctx *c) {
-  mtxd::WaveBuffers b;
-  b.ray_o[0] = (float4 *)c->ray_o.p;
-  b.ray_o[1] = b.ray_o[0] + c->capacity;
-  b.ray_d[0] = (float4 *)c->ray_d.p;
-  b.ray_d[1] = b.ray_d[0] + c->capacity;
-  b.ray_par = 0;
-  b.thr[0] = (float4 *)c->thr.p;
-  b.thr[1] = b.thr[0] + c->capacity;
-  for (int k = 0; k < 3; ++k) b.L[k] = (float4 *)c->L.p + (size_t)k * c->capacity;
-  b.prev[0] = (float4 *)c->prev.p;
-  b.prev[1] = b.prev[0] + c->capacity;
-  for (int k = 0; k < 3; ++k) b.misc[k] = (uint4 *)c->misc.p + (size_t)k * c->capacity;
-  b.pos = (float2 *)c->pos.p;
-  b.hit = (float4 *)c->hit.p;
-  b.queue[0] = (uint32_t *)c->q0.p;
-  b.queue[1] = (uint32_t *)c->q1.p;
-  b.shadow = (float4 *)c->shadow.p;
-  b.counters = (uint32_t *)c->counters.p;
-  b.xheads = (uint32_t *)c->xheads.p;
+// Sub-plane k of a wave's plane, typed: T is the plane's entry.
+template <class T, PlaneId id>
+T *plane_at(const Wave &w, uint32_t k = 0) {
+  static_assert(sizeof(T) == kPlanes[id].elem, "entry type and plane description disagree");
+  return (T *)w.plane[id].p + (size_t)k * w.capacity;
+}
+
+// The kernels' view of a wave. Shared by both waves: stats, the PSSMLT
+// planes (single-wave renders only); rs_xs / rs_ns are set by render_restir.
+mtxd::WaveBuffers views(mtx_ctx *c, const Wave &w) {
+  mtxd::WaveBuffers b{};
+  for (uint32_t k = 0; k < 2; ++k) {
+    b.ray_o[k] = plane_at<float4, kRayO>(w, k);
+    b.ray_d[k] = plane_at<float4, kRayD>(w, k);
+    b.thr[k] = plane_at<float4, kThr>(w, k);
+    b.prev[k] = plane_at<float4, kPrev>(w, k);
+  }
+  for (uint32_t k = 0; k < 3; ++k) {
+    b.L[k] = plane_at<float4, kL>(w, k);
+    b.misc[k] = plane_at<uint4, kMisc>(w, k);
+  }
+  b.pos = plane_at<float2, kPos>(w);
+  b.hit = plane_at<float4, kHit>(w);
+  b.queue[0] = plane_at<uint32_t, kQ0>(w);
+  b.queue[1] = plane_at<uint32_t, kQ1>(w);
+  b.shadow = plane_at<float4, kShadow>(w);  // the kernels place its four planes (shadow_word)
+  b.counters = (uint32_t *)w.counters.p;
+  b.xheads = (uint32_t *)w.xheads.p;
   b.stats = (unsigned long long *)c->stats.p;
-  b.capacity = c->capacity;
+  b.capacity = w.capacity;
   b.mlt_cur = (float4 *)c->mlt_cur.p;
   b.mlt_L = (float4 *)c->mlt_L.p;
   b.mlt_prop = (float2 *)c->mlt_prop.p;
@@ -819,127 +850,63 @@ mtxd::WaveBuffers buffers(mtx_ctx *c) {
   b.vprop = (float4 *)c->vprop.p;
   b.vpath_es = (float2 *)c->vpath_es.p;
   b.vprop_es = (float2 *)c->vprop_es.p;
-  b.cq_p = (float4 *)c->cq_p.p;
-  b.cq_d = (float4 *)c->cq_d.p;
-  b.cq_t = (float4 *)c->cq_t.p;
-  b.cq_count = (uint32_t *)c->cq_count.p;
-  return b;
-}
-
-// The second wavefront (Wave2): buffers for `cap` paths, its stream and
-// events, and a traversal spill area of its own (two trace launches may run
-// at once).
-int ensure_wavefront2(mtx_ctx *c, uint32_t cap, uint32_t max_depth) {
-  int rc;
-  Wave2 &w = c->w2;
-  if (!w.stream) {
-    HIP_TRY(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&w.start, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
-  }
-  if (cap > w.capacity) {
-    for (DevBuf *b : {&w.ray_o, &w.ray_d, &w.thr, &w.prev})
-      if ((rc = dalloc(*b, 32ull * cap))) return rc;
-    for (DevBuf *b : {&w.L, &w.misc})
-      if ((rc = dalloc(*b, 48ull * cap))) return rc;
-    if ((rc = dalloc(w.hit, 16ull * cap))) return rc;
-    if ((rc = dalloc(w.pos, 8ull * cap))) return rc;
-    if ((rc = dalloc(w.q0, 4ull * cap))) return rc;
-    if ((rc = dalloc(w.q1, 4ull * cap))) return rc;
-    if ((rc = dalloc(w.shadow, 64ull * cap))) return rc;  // four planes of 16-B word groups
-    w.capacity = cap;
-  }
-  if ((rc = dalloc(w.counters, 16ull * (max_depth + 2)))) return rc;
-  if ((rc = dalloc(w.xheads, 8ull * mtxd::kXSlotWords * (max_depth + 2)))) return rc;
-  const mtxd::DevScene &s = c->scene;
-  if ((rc = dalloc(w.stack_ovf, mtxd::stack_ovf_bytes(s)))) return rc;
-  return MTX_OK;
-}
-
-mtxd::WaveBuffers buffers2(mtx_ctx *c) {
-  mtxd::WaveBuffers b = buffers(c);  // shared: stats, the PSSMLT / cache planes (unused by this path)
-  Wave2 &w = c->w2;
-  b.ray_o[0] = (float4 *)w.ray_o.p;
-  b.ray_o[1] = b.ray_o[0] + w.capacity;
-  b.ray_d[0] = (float4 *)w.ray_d.p;
-  b.ray_d[1] = b.ray_d[0] + w.capacity;
-  b.thr[0] = (float4 *)w.thr.p;
-  b.thr[1] = b.thr[0] + w.capacity;
-  for (int k = 0; k < 3; ++k) b.L[k] = (float4 *)w.L.p + (size_t)k * w.capacity;
-  b.prev[0] = (float4 *)w.prev.p;
-  b.prev[1] = b.prev[0] + w.capacity;
-  for (int k = 0; k < 3; ++k) b.misc[k] = (uint4 *)w.misc.p + (size_t)k * w.capacity;
-  b.pos = (float2 *)w.pos.p;
-  b.hit = (float4 *)w.hit.p;
-  b.queue[0] = (uint32_t *)w.q0.p;
-  b.queue[1] = (uint32_t *)w.q1.p;
-  b.shadow = (float4 *)w.shadow.p;
-  b.counters = (uint32_t *)w.counters.p;
-  b.xheads = (uint32_t *)w.xheads.p;
-  b.capacity = w.capacity;
-  b.cq_p = (float4 *)w.cq_p.p;  // null unless ensure_cache2
+  b.cq_p = (float4 *)w.cq_p.p;  // null unless ensure_cache
   b.cq_d = (float4 *)w.cq_d.p;
   b.cq_t = (float4 *)w.cq_t.p;
   b.cq_count = (uint32_t *)w.cq_count.p;
   return b;
 }
 
+// The scene as wave `w` traces it: the context's, with the wave's spill area.
+mtxd::DevScene wave_scene(const mtx_ctx *c, const Wave &w) {
+  mtxd::DevScene s = c->scene;
+  s.stack_ovf = w.stack_ovf.p;
+  return s;
+}
+
 // Zeroes a chunk's queue counters and the per-XCD claim cursors.
 hipError_t reset_counters(const mtxd::WaveBuffers &b, uint32_t depth, hipStream_t st) {
-  hipError_t e = hipMemsetAsync(b.counters, 0, 16ull * (depth + 2), st);
+  hipError_t e = hipMemsetAsync(b.counters, 0, counters_bytes(depth), st);
   if (e != hipSuccess) return e;
-  return hipMemsetAsync(b.xheads, 0, 8ull * mtxd::kXSlotWords * (depth + 2), st);
+  return hipMemsetAsync(b.xheads, 0, xheads_bytes(depth), st);
 }
 
 int ensure_mlt(mtx_ctx *c, uint32_t cap, uint32_t max_depth, bool emitter_samples) {
   int rc;
-  if (emitter_samples && (!c->vpath_es.p || c->mlt_es_capacity != c->capacity || max_depth > c->mlt_es_depth)) {
-    const size_t wc = c->capacity;
+  const size_t wc = c->wave[0].capacity;  // the chains run on wave 0
+  if (emitter_samples && (!c->vpath_es.p || c->mlt_es_capacity != wc || max_depth > c->mlt_es_depth)) {
     if ((rc = dalloc(c->vpath_es, 8 * wc * max_depth))) return rc;
     if ((rc = dalloc(c->vprop_es, 8 * wc * max_depth))) return rc;
-    c->mlt_es_capacity = c->capacity;
+    c->mlt_es_capacity = wc;
     c->mlt_es_depth = max_depth;
   }
-  if (cap > c->mlt_capacity || max_depth > c->mlt_depth || c->mlt_capacity != c->capacity) {
+  if (cap > c->mlt_capacity || max_depth > c->mlt_depth || c->mlt_capacity != wc) {
     // vertex buffers are indexed [depth * wavefront capacity + chain]
-    const size_t wc = c->capacity;
     if ((rc = dalloc(c->mlt_cur, 16 * wc))) return rc;
     if ((rc = dalloc(c->mlt_L, 16 * wc))) return rc;
     if ((rc = dalloc(c->mlt_prop, 8 * wc))) return rc;
     if ((rc = dalloc(c->vpath, 16 * wc * max_depth))) return rc;
     if ((rc = dalloc(c->vprop, 16 * wc * max_depth))) return rc;
-    c->mlt_capacity = c->capacity;
+    c->mlt_capacity = wc;
     c->mlt_depth = max_depth;
   }
   return MTX_OK;
 }
 
-// NRC radiance-cache buffers for `cap` paths (queries <= paths).
-int ensure_cache(mtx_ctx *c, uint32_t cap) {
+// Wave `w`'s NRC radiance-cache buffers for `cap` paths (queries <= paths).
+// Callers ensure wave 0's first, so a missing field is refused before
+// anything is allocated for either wave.
+int ensure_cache(mtx_ctx *c, Wave &w, uint32_t cap) {
   int rc;
   if (!c->has_field) {
     mtx_set_error("mtx_render: NRC cache requested but no radiance field uploaded (mtx_field_upload)");
     return MTX_E_ARG;
   }
-  if ((rc = dalloc(c->cq_p, 16ull * cap))) return rc;
-  if ((rc = dalloc(c->cq_d, 16ull * cap))) return rc;
-  if ((rc = dalloc(c->cq_t, 16ull * cap))) return rc;
-  if ((rc = dalloc(c->cq_count, 16))) return rc;
-  if ((rc = dalloc(c->f_feat, 128ull * cap))) return rc;
-  if ((rc = dalloc(c->f_out, 12ull * cap))) return rc;
-  return MTX_OK;
-}
-
-// The second wavefront's cache-query buffers (two-stream NRC + cache render).
-int ensure_cache2(mtx_ctx *c, uint32_t cap) {
-  int rc;
-  Wave2 &w = c->w2;
-  if ((rc = dalloc(w.cq_p, 16ull * cap))) return rc;
-  if ((rc = dalloc(w.cq_d, 16ull * cap))) return rc;
-  if ((rc = dalloc(w.cq_t, 16ull * cap))) return rc;
+  for (DevBuf *q : {&w.cq_p, &w.cq_d, &w.cq_t})
+    if ((rc = dalloc(*q, kQueryBytes * cap))) return rc;
   if ((rc = dalloc(w.cq_count, 16))) return rc;
-  if ((rc = dalloc(w.f_feat, 128ull * cap))) return rc;
-  if ((rc = dalloc(w.f_out, 12ull * cap))) return rc;
+  if ((rc = dalloc(w.f_feat, kFeatBytes * cap))) return rc;
+  if ((rc = dalloc(w.f_out, kOutBytes * cap))) return rc;
   return MTX_OK;
 }
 
@@ -1007,40 +974,38 @@ struct Timer {
   }
 };
 
-// Encode + MLP + L += T * out for the chunk's compacted cache queries (on
-// `stream` with the feature / output buffers of the chunk's wavefront: the
-// context's by default, the second wavefront's in a two-stream render).
-int run_cache(mtx_ctx *c, const mtxd::WaveBuffers &b, uint32_t cap, Timer &tm, bool nerad_render = false,
-               hipStream_t stream = nullptr, DevBuf *feat = nullptr, DevBuf *out = nullptr, DevBuf *perm_buf = nullptr,
-               DevBuf *cursor_buf = nullptr) {
-  hipStream_t st = stream ? stream : c->stream;
-  DevBuf &f_feat = feat ? *feat : c->f_feat, &f_out = out ? *out : c->f_out;
+// Encode + MLP + L += T * out for the compacted cache queries of a chunk of
+// wave `w` (views `b`), on the wave's stream with the wave's buffers.
+int run_cache(mtx_ctx *c, Wave &w, const mtxd::WaveBuffers &b, uint32_t cap, Timer &tm, bool nerad_render) {
+  hipStream_t st = w.stream;
+  DevBuf &f_feat = w.f_feat, &f_out = w.f_out;
   const uint32_t *perm = nullptr;
   int xcd_split = 0;
   hipEvent_t e = tm.begin(4, st);
   if (c->cache_sort == 2 && !nerad_render) {
     // region-grouped rows, the blocks of each XCD on one eighth of them
     // (field.hip k_field_encode xcd_split): device-only, no host round trip
-    DevBuf &pb = perm_buf ? *perm_buf : c->cq_perm, &cb = cursor_buf ? *cursor_buf : c->cq_keys;
-    if (!dalloc(pb, 4ull * cap) && !dalloc(cb, 4ull * 32768)) {
-      mtxd::field_bucket_queries(c->field, b.cq_p, b.cq_count, cap, (uint32_t *)cb.p, (uint32_t *)pb.p, c->n_cu, st);
-      perm = (const uint32_t *)pb.p;
+    if (!dalloc(w.cq_perm, 4ull * cap) && !dalloc(w.cq_cursor, 4ull * 32768)) {
+      mtxd::field_bucket_queries(c->field, b.cq_p, b.cq_count, cap, (uint32_t *)w.cq_cursor.p,
+                                 (uint32_t *)w.cq_perm.p, c->n_cu, st);
+      perm = (const uint32_t *)w.cq_perm.p;
       xcd_split = 1;
     }
-  } else if (c->cache_sort && !nerad_render && st == c->stream) {
+  } else if (c->cache_sort && !nerad_render && &w == &c->wave[0]) {
     // encode the queries in Morton order (a stable sort of 24-bit cell codes
     // with the hash-grid group-by): the hash-grid corner gathers of
     // neighbouring rows then share table lines. The MLP row order follows;
     // k_cache_apply maps row q back to query perm[q]. Results are unchanged
-    // (every query's features and MLP column are its own).
+    // (every query's features and MLP column are its own). Wave 0 only (a
+    // host sync per chunk; mtx_render runs such a render on one stream).
+    DevBuf &keys = w.cq_cursor;
     uint32_t nq = 0;
-    if (hipMemcpyAsync(&nq, b.cq_count, 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
-        hipStreamSynchronize(c->stream) == hipSuccess && nq > 0 && !dalloc(c->cq_keys, 4ull * nq) &&
-        !dalloc(c->cq_perm, 4ull * nq) && !dalloc(c->cq_ws, mtxd::sort24_workspace_bytes(nq))) {
-      mtxd::field_morton_keys(c->field, b.cq_p, nq, (uint32_t *)c->cq_keys.p, c->stream);
-      if (mtxd::sort24((const uint32_t *)c->cq_keys.p, nq, (uint32_t *)c->cq_perm.p, c->cq_ws.p, c->stream) ==
-          MTX_OK)
-        perm = (const uint32_t *)c->cq_perm.p;
+    if (hipMemcpyAsync(&nq, b.cq_count, 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+        hipStreamSynchronize(st) == hipSuccess && nq > 0 && !dalloc(keys, 4ull * nq) &&
+        !dalloc(w.cq_perm, 4ull * nq) && !dalloc(c->cq_ws, mtxd::sort24_workspace_bytes(nq))) {
+      mtxd::field_morton_keys(c->field, b.cq_p, nq, (uint32_t *)keys.p, st);
+      if (mtxd::sort24((const uint32_t *)keys.p, nq, (uint32_t *)w.cq_perm.p, c->cq_ws.p, st) == MTX_OK)
+        perm = (const uint32_t *)w.cq_perm.p;
     }
   }
   // the fused pass only when its LDS fits a workgroup (n_hidden <= 14)
@@ -1128,12 +1093,12 @@ void finish_bounces(const mtxd::WaveBuffers &b, const mtxd::ChunkParams &p, hipS
     mtxd::launch_flush_tail(b, bounce_iters(p), b.capacity, p.integrator, st);
 }
 
-// Runs one chunk's bounce loop (rays already generated, counters[0] set).
-void run_bounces(mtx_ctx *c, const mtxd::WaveBuffers &b, const mtxd::ChunkParams &p, Timer &tm,
-                 uint64_t *n_trace, uint64_t *n_shadow, const mtxd::DevScene *scene = nullptr,
-                 hipStream_t stream = nullptr) {
-  const mtxd::DevScene &s = scene ? *scene : c->scene;
-  hipStream_t st = stream ? stream : c->stream;
+// Runs the bounce loop of one chunk of wave `w` (views `b`; rays already
+// generated, counters[0] set) on the wave's stream.
+void run_bounces(mtx_ctx *c, const Wave &w, const mtxd::WaveBuffers &b, const mtxd::ChunkParams &p, Timer &tm,
+                 uint64_t *n_trace, uint64_t *n_shadow) {
+  const mtxd::DevScene s = wave_scene(c, w);
+  hipStream_t st = w.stream;
   const uint32_t depth_iters = bounce_iters(p);
   for (uint32_t bounce = 0; bounce < depth_iters; ++bounce) {
     launch_bounce(c, b, p, tm, n_trace, n_shadow, s, st, bounce);
@@ -1243,7 +1208,8 @@ int render_restir(mtx_ctx *c, const mtx_render_args *a, float4 *film_dev, Timer 
   const uint32_t lane0 = a->y0 * W * spp, nb = (a->y1 - a->y0) * W * spp;
   const uint32_t depth = std::max<uint32_t>(a->max_depth, 1);
   int rc;
-  if ((rc = ensure_wavefront(c, nb, depth))) return rc;
+  Wave *wv = c->wave;
+  if ((rc = ensure_wave(c, wv[0], nb, depth))) return rc;
   if ((rc = ensure_restir(c, n))) return rc;
   if (run_a && a->frame != 0 && !c->rs_valid) {
     mtx_set_error("mtx_render: ReSTIR GI frame %u without the state of frame 0 (film size or scene changed?)",
@@ -1266,7 +1232,7 @@ int render_restir(mtx_ctx *c, const mtx_render_args *a, float4 *film_dev, Timer 
     c->rs_prev_cam = cam;
     c->rs_cur = 0;
   }
-  mtxd::WaveBuffers b = buffers(c);
+  mtxd::WaveBuffers b = views(c, wv[0]);
   mtxd::RestirBuffers r{};
   r.cur = (float4 *)c->rs_samp[c->rs_cur].p;
   r.prev = a->frame == 0 ? r.cur : (const float4 *)c->rs_samp[c->rs_cur ^ 1].p;
@@ -1334,26 +1300,23 @@ int render_restir(mtx_ctx *c, const mtx_render_args *a, float4 *film_dev, Timer 
     const bool two = !mega_all && c->streams > 1 && rows >= 2 && nb >= (1u << 16);
     if (two) tm.streams = 2;
     const uint32_t ym = two ? a->y0 + rows / 2 : a->y1;
-    mtxd::DevScene s2 = c->scene;
-    mtxd::WaveBuffers bw2{};
-    if (two) {
-      if ((rc = ensure_wavefront2(c, (a->y1 - ym) * W * spp, depth))) return rc;
-      bw2 = buffers2(c);
-      s2.stack_ovf = c->w2.stack_ovf.p;
-      HIP_TRY(hipEventRecord(c->w2.start, st));  // after the frame-0 clears
-      HIP_TRY(hipStreamWaitEvent(c->w2.stream, c->w2.start, 0));
+    if (two) {  // wave 1 holds the second half only
+      if ((rc = ensure_wave(c, wv[1], (a->y1 - ym) * W * spp, depth))) return rc;
+      HIP_TRY(hipEventRecord(wv[1].start, st));  // after the frame-0 clears
+      HIP_TRY(hipStreamWaitEvent(wv[1].stream, wv[1].start, 0));
     }
     // The halves' launches are enqueued interleaved, step by step (prologue,
     // each bounce, epilogue), so the second stream starts at once instead of
     // after the host has queued all of the first half's launches.
     const int halves = two ? 2 : 1;
-    hipStream_t sh[2] = {st, c->w2.stream};
+    const mtxd::DevScene sc[2] = {wave_scene(c, wv[0]), wave_scene(c, wv[1])};
+    hipStream_t sh[2] = {st, wv[1].stream};
     if (mega_all && c->rs_fused) {
       // the whole stage A up to k_rs_collect in one per-lane launch
       // (kernels.hip k_rs_stage_a), then the temporal pass
       HIP_TRY(reset_counters(b, depth, st));
       e = tm.begin(0, st);
-      mtxd::launch_rs_stage_a(c->scene, b, p, r,
+      mtxd::launch_rs_stage_a(sc[0], b, p, r,
                               std::max(1, std::min<int>(c->mega_grid, (nb + mtxd::kShadeBlock - 1) / mtxd::kShadeBlock)),
                               st);
       tm.end(0, e, st);
@@ -1361,13 +1324,12 @@ int render_restir(mtx_ctx *c, const mtx_render_args *a, float4 *film_dev, Timer 
       mtxd::launch_restir_temporal(r, p, st);
     }
     const bool fused = mega_all && c->rs_fused;
-    const mtxd::DevScene *sc[2] = {&c->scene, &s2};
     mtxd::WaveBuffers bh[2], b1[2];
     mtxd::ChunkParams ph[2];
     mtxd::RestirBuffers rh[2];
     for (int h = 0; h < (fused ? 0 : halves); ++h) {
       const uint32_t ya = h ? ym : a->y0, yb = h ? a->y1 : ym;
-      bh[h] = h ? bw2 : b;
+      bh[h] = h ? views(c, wv[1]) : b;
       bh[h].rs_xs = b.rs_xs + (size_t)(ya - a->y0) * W * spp;  // path-indexed within the half
       bh[h].rs_ns = b.rs_ns + (size_t)(ya - a->y0) * W * spp;
       ph[h] = p;
@@ -1379,13 +1341,13 @@ int render_restir(mtx_ctx *c, const mtx_render_args *a, float4 *film_dev, Timer 
       rh[h].nb = ph[h].n_paths;
       // sample_initial: primary rays and their closest hits
       HIP_TRY(reset_counters(bh[h], depth, sh[h]));
-      mtxd::launch_raygen_camera(*sc[h], bh[h], ph[h], sh[h]);
+      mtxd::launch_raygen_camera(sc[h], bh[h], ph[h], sh[h]);
       e = tm.begin(0, sh[h]);
-      mtxd::launch_trace_closest(*sc[h], bh[h], 0, ph[h].stats, c->closest_grid, sh[h]);
+      mtxd::launch_trace_closest(sc[h], bh[h], 0, ph[h].stats, c->closest_grid, sh[h]);
       tm.end(0, e, sh[h]);
       ++*n_trace;
       HIP_TRY(reset_counters(bh[h], depth, sh[h]));
-      mtxd::launch_restir_begin(*sc[h], bh[h], ph[h], rh[h], sh[h]);
+      mtxd::launch_restir_begin(sc[h], bh[h], ph[h], rh[h], sh[h]);
       b1[h] = bh[h];  // k_rs_begin left the secondary rays in the parity-1 planes
       b1[h].ray_par = 1;
     }
@@ -1397,7 +1359,7 @@ int render_restir(mtx_ctx *c, const mtx_render_args *a, float4 *film_dev, Timer 
       mega[h] = mega_all;
       if (!mega[h]) continue;
       e = tm.begin(0, sh[h]);
-      mtxd::launch_path_mega(*sc[h], b1[h], ph[h],
+      mtxd::launch_path_mega(sc[h], b1[h], ph[h],
                              std::max(1, std::min<int>(c->mega_grid, (ph[h].n_paths + mtxd::kShadeBlock - 1) /
                                                                          mtxd::kShadeBlock)),
                              sh[h]);
@@ -1407,15 +1369,15 @@ int render_restir(mtx_ctx *c, const mtx_render_args *a, float4 *film_dev, Timer 
     const uint32_t iters = fused ? 0u : bounce_iters(p);
     for (uint32_t bounce = 0; bounce < iters; ++bounce)
       for (int h = 0; h < halves; ++h)
-        if (!mega[h]) launch_bounce(c, b1[h], ph[h], tm, n_trace, n_shadow, *sc[h], sh[h], bounce);
+        if (!mega[h]) launch_bounce(c, b1[h], ph[h], tm, n_trace, n_shadow, sc[h], sh[h], bounce);
     for (int h = 0; h < (fused ? 0 : halves); ++h) {
       if (!mega[h]) finish_bounces(b1[h], ph[h], sh[h]);
       mtxd::launch_restir_collect(bh[h], ph[h], rh[h], sh[h]);
       mtxd::launch_restir_temporal(rh[h], ph[h], sh[h]);
     }
     if (two) {  // stage B reads every lane of the band
-      HIP_TRY(hipEventRecord(c->w2.done, c->w2.stream));
-      HIP_TRY(hipStreamWaitEvent(st, c->w2.done, 0));
+      HIP_TRY(hipEventRecord(wv[1].done, wv[1].stream));
+      HIP_TRY(hipStreamWaitEvent(st, wv[1].done, 0));
     }
   }
   if (run_b) {
@@ -1487,7 +1449,7 @@ int mtx_render(mtx_ctx *c, const mtx_render_args *a, float *film_rgbw, int film_
   const bool nrc_cache = a->integrator == MTX_INT_NRC && (a->flags & 4u);
   const bool nerad_render = a->integrator == MTX_INT_NERAD;
   const bool mlt = a->integrator == MTX_INT_PSSMLT_SIMPLE || a->integrator == MTX_INT_PSSMLT_PATH;
-  // two wavefronts on two streams (Wave2): the band splits into at least two
+  // two wavefronts on two streams (wave[0], wave[1]): the band splits into at least two
   // chunks that alternate between them (the caller's chunk size still caps a
   // chunk), so one chunk's kernels fill the tails of the other's persistent
   // trace launches (~0.2 ms per launch that does not shrink with the rays).
@@ -1508,10 +1470,12 @@ int mtx_render(mtx_ctx *c, const mtx_render_args *a, float *film_rgbw, int film_
   uint32_t px_per_chunk = std::min(std::max<uint32_t>(1, chunk_paths / a->spp), band_px);
   if (two) px_per_chunk = std::min(px_per_chunk, (band_px + 1) / 2);
   const uint32_t cap = px_per_chunk * a->spp;
-  if ((rc = ensure_wavefront(c, cap, std::max<uint32_t>(a->max_depth, 1)))) return rc;
-  if (two && (rc = ensure_wavefront2(c, cap, std::max<uint32_t>(a->max_depth, 1)))) return rc;
-  if ((nrc_cache || nerad_render) && (rc = ensure_cache(c, cap))) return rc;
-  if (two && nrc_cache && (rc = ensure_cache2(c, cap))) return rc;
+  const uint32_t depth = std::max<uint32_t>(a->max_depth, 1);
+  const int n_waves = two ? 2 : 1;
+  for (int k = 0; k < n_waves; ++k) {
+    if ((rc = ensure_wave(c, c->wave[k], cap, depth))) return rc;
+    if ((nrc_cache || nerad_render) && (rc = ensure_cache(c, c->wave[k], cap))) return rc;
+  }
   // sample-sharded film renders: 8 partial slots (GPU-count-invariant films,
   // DESIGN.md "Film"); PSSMLT splats and ReSTIR frames: one
   const uint32_t film_slots = (mlt || a->integrator == MTX_INT_RESTIR_GI) ? 1u : 8u;
@@ -1551,30 +1515,29 @@ int mtx_render(mtx_ctx *c, const mtx_render_args *a, float *film_rgbw, int film_
     return fill_stats(c, stats, want_stats, tm, n_trace, n_shadow, (uint64_t)W * H * a->spp);
   }
   if (mlt) {
-    if ((rc = ensure_mlt(c, cap, std::max<uint32_t>(a->max_depth, 1), a->integrator == MTX_INT_PSSMLT_PATH)))
-      return rc;
+    if ((rc = ensure_mlt(c, cap, depth, a->integrator == MTX_INT_PSSMLT_PATH))) return rc;
     HIP_TRY(hipMemsetAsync(c->contrib.p, 0, taps * 16 * band_px, c->stream));
   }
-  mtxd::WaveBuffers b = buffers(c);
-  if (want_stats) HIP_TRY(hipMemsetAsync(b.stats, 0, 64, c->stream));
+  // every allocation is made: the views of the waves this render uses
+  mtxd::WaveBuffers views_of[2];
+  for (int k = 0; k < n_waves; ++k) views_of[k] = views(c, c->wave[k]);
+  if (want_stats) HIP_TRY(hipMemsetAsync(c->stats.p, 0, 64, c->stream));
   uint64_t n_trace = 0, n_shadow = 0;
   hipEvent_t e_all = tm.begin(3);
-  mtxd::WaveBuffers b2{};
-  mtxd::DevScene s2{};
   if (two) {
     // the second stream starts after everything queued on the first
-    b2 = buffers2(c);
-    s2 = c->scene;
-    s2.stack_ovf = c->w2.stack_ovf.p;
-    HIP_TRY(hipEventRecord(c->w2.start, c->stream));
-    HIP_TRY(hipStreamWaitEvent(c->w2.stream, c->w2.start, 0));
+    HIP_TRY(hipEventRecord(c->wave[1].start, c->stream));
+    HIP_TRY(hipStreamWaitEvent(c->wave[1].stream, c->wave[1].start, 0));
   }
   uint32_t chunk_index = 0;
   for (uint32_t px0 = a->y0 * W; px0 < a->y1 * W; px0 += px_per_chunk, ++chunk_index) {
-    const bool second = two && (chunk_index & 1u);
-    hipStream_t st = second ? c->w2.stream : c->stream;
-    const mtxd::WaveBuffers &bc = second ? b2 : b;
-    const mtxd::DevScene &sc = second ? s2 : c->scene;
+    // chunks alternate between the waves (PSSMLT, the nerad render and the
+    // Morton-sorted cache are never two-stream renders: wave 0)
+    const int wi = two ? (int)(chunk_index & 1u) : 0;
+    Wave &w = c->wave[wi];
+    hipStream_t st = w.stream;
+    const mtxd::WaveBuffers &bc = views_of[wi];
+    const mtxd::DevScene sc = wave_scene(c, w);
     mtxd::ChunkParams p{};
     p.integrator = a->integrator;
     p.max_depth = a->max_depth;
@@ -1608,38 +1571,30 @@ int mtx_render(mtx_ctx *c, const mtx_render_args *a, float *film_rgbw, int film_
     if (mlt) {
       // Pssmlt.render (pssmlt.py:167-228): all iterations of this chunk's chains
       const uint32_t iters = a->iterations ? a->iterations : 200;
-      mtxd::launch_mlt_init(b, p, c->stream);
+      mtxd::launch_mlt_init(bc, p, st);
       for (uint32_t it = 0; it < iters; ++it) {
         p.large_step = (it % 50 == 0) ? 1u : 0u;  // reset_interval = 50 (:209)
-        HIP_TRY(reset_counters(b, std::max<uint32_t>(a->max_depth, 1), c->stream));
-        mtxd::launch_mlt_begin(c->scene, b, p, c->stream);
-        run_bounces(c, b, p, tm, &n_trace, &n_shadow);
-        mtxd::launch_mlt_end(b, p, c->stream);
-        if (it % 50 > 40) mtxd::launch_mlt_film(b, p, (float4 *)c->contrib.p, c->stream);  // bootstrapping = 40
+        HIP_TRY(reset_counters(bc, depth, st));
+        mtxd::launch_mlt_begin(sc, bc, p, st);
+        run_bounces(c, w, bc, p, tm, &n_trace, &n_shadow);
+        mtxd::launch_mlt_end(bc, p, st);
+        if (it % 50 > 40) mtxd::launch_mlt_film(bc, p, (float4 *)c->contrib.p, st);  // bootstrapping = 40
       }
       continue;
     }
-    HIP_TRY(reset_counters(bc, std::max<uint32_t>(a->max_depth, 1), st));
+    HIP_TRY(reset_counters(bc, depth, st));
     if (nrc_cache || nerad_render) HIP_TRY(hipMemsetAsync(bc.cq_count, 0, 4, st));
     if (p.cam0)  // what raygen's thread 0 did: the bounce-0 queue holds every path
       HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)bc.counters, (int)p.n_paths, 1, st));
     else
       mtxd::launch_raygen_camera(sc, bc, p, st);
-    run_bounces(c, bc, p, tm, &n_trace, &n_shadow, &sc, st);
-    if (nrc_cache) {
-      if (second)
-        rc = run_cache(c, bc, p.n_paths, tm, false, st, &c->w2.f_feat, &c->w2.f_out, &c->w2.cq_perm,
-                       &c->w2.cq_cursor);
-      else
-        rc = run_cache(c, b, p.n_paths, tm);
-      if (rc) return rc;
-    }
-    if (nerad_render && (rc = run_cache(c, b, p.n_paths, tm, true))) return rc;
+    run_bounces(c, w, bc, p, tm, &n_trace, &n_shadow);
+    if ((nrc_cache || nerad_render) && (rc = run_cache(c, w, bc, p.n_paths, tm, nerad_render))) return rc;
     mtxd::launch_film_src(bc, p, (float4 *)c->contrib.p, st);
   }
   if (two) {  // the film gather reads both wavefronts' contributions
-    HIP_TRY(hipEventRecord(c->w2.done, c->w2.stream));
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->w2.done, 0));
+    HIP_TRY(hipEventRecord(c->wave[1].done, c->wave[1].stream));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->wave[1].done, 0));
   }
   mtxd::launch_film_gather((const float4 *)c->contrib.p, film_dev, W, a->y0, a->y1, film_slots, slot_mask, a->rfilter,
                            c->stream);
@@ -1968,17 +1923,18 @@ static int sample_rays_impl(mtx_ctx *c, const mtx_render_args *a, uint64_t n, co
   HIP_TRY(hipSetDevice(c->device));
   const uint32_t chunk = a->chunk_paths ? a->chunk_paths : default_chunk(c, a, 1u, false);
   const uint32_t cap = (uint32_t)std::min<uint64_t>(n, chunk);
-  if ((rc = ensure_wavefront(c, cap, std::max<uint32_t>(a->max_depth, 1)))) return rc;
+  Wave &w = c->wave[0];
+  if ((rc = ensure_wave(c, w, cap, std::max<uint32_t>(a->max_depth, 1)))) return rc;
   const bool nrc_cache = a->integrator == MTX_INT_NRC && (a->flags & 4u);
   const bool nerad_render = a->integrator == MTX_INT_NERAD;
-  if ((nrc_cache || nerad_render) && (rc = ensure_cache(c, cap))) return rc;
+  if ((nrc_cache || nerad_render) && (rc = ensure_cache(c, w, cap))) return rc;
   if (!dev) {
     if ((rc = dalloc(c->s0, 24ull * cap))) return rc;
     if ((rc = dalloc(c->s1, 4ull * cap))) return rc;
     if ((rc = dalloc(c->s2, 12ull * cap))) return rc;
     if ((rc = dalloc(c->s3, 1ull * cap))) return rc;
   }
-  mtxd::WaveBuffers b = buffers(c);
+  mtxd::WaveBuffers b = views(c, w);
   Timer tm{c, false};
   uint64_t nt = 0, ns = 0;
   for (uint64_t off = 0; off < n; off += cap) {
@@ -2008,9 +1964,8 @@ static int sample_rays_impl(mtx_ctx *c, const mtx_render_args *a, uint64_t n, co
     HIP_TRY(reset_counters(b, std::max<uint32_t>(a->max_depth, 1), c->stream));
     if (nrc_cache || nerad_render) HIP_TRY(hipMemsetAsync(b.cq_count, 0, 4, c->stream));
     mtxd::launch_raygen_rays(c->scene, b, p, d_rays, d_lanes, rng_skip, c->stream);
-    run_bounces(c, b, p, tm, &nt, &ns);
-    if (nrc_cache && (rc = run_cache(c, b, m, tm))) return rc;
-    if (nerad_render && (rc = run_cache(c, b, m, tm, true))) return rc;
+    run_bounces(c, w, b, p, tm, &nt, &ns);
+    if ((nrc_cache || nerad_render) && (rc = run_cache(c, w, b, m, tm, nerad_render))) return rc;
     mtxd::launch_collect(b, p, d_L, d_valid, c->stream);
     HIP_TRY(hipGetLastError());
     if (!dev) {
@@ -2079,23 +2034,30 @@ static int trace_impl(mtx_ctx *c, uint64_t n, const float *rays, int any_hit, ui
   return MTX_OK;
 }
 
+}  // extern "C"
+
 // ------------------------------- primitives -------------------------------
 
-// HIP-event bracket around the device work of one primitive call.
-static int prim_timer_begin(mtx_ctx *c) {
+// Runs the device work of one primitive call: `launch` enqueues the
+// primitive's kernels on the context's stream and returns an MTX code. The
+// event pair encloses those kernels only -- callers stage, range-check and
+// copy back outside it -- and their time is what mtx_last_device_ms reports.
+// The stream is idle on return.
+template <class Launch>
+static int prim_run(mtx_ctx *c, Launch launch) {
   for (int k = 0; k < 2; ++k)
     if (!c->prim_ev[k]) HIP_TRY(hipEventCreate(&c->prim_ev[k]));
   HIP_TRY(hipEventRecord(c->prim_ev[0], c->stream));
-  return MTX_OK;
-}
-static int prim_timer_end(mtx_ctx *c) {
+  if (int rc = launch()) return rc;
   HIP_TRY(hipEventRecord(c->prim_ev[1], c->stream));
-  return MTX_OK;
-}
-static void prim_timer_read(mtx_ctx *c) {
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, c->prim_ev[0], c->prim_ev[1]) == hipSuccess) c->last_device_ms = ms;
+  return MTX_OK;
 }
+
+extern "C" {
 
 double mtx_last_device_ms(mtx_ctx *c) { return c ? c->last_device_ms : 0.0; }
 
@@ -2172,6 +2134,35 @@ static int field_check(mtx_ctx *c, uint64_t n) {
   return MTX_OK;
 }
 
+// The encoder over the n staged queries and the MLP over n feature rows;
+// wave 0's feature and output buffers are the field entry points' scratch.
+static int field_encode_staged(mtx_ctx *c, uint64_t n) {
+  return mtxd::field_encode(c->field, (const float4 *)c->fq_p.p, (const float4 *)c->fq_d.p, nullptr, (uint32_t)n,
+                            (uint16_t *)c->wave[0].f_feat.p, c->stream);
+}
+static int field_mlp_staged(mtx_ctx *c, uint64_t n) {
+  return mtxd::field_mlp((const uint16_t *)c->wave[0].f_feat.p, nullptr, (uint32_t)n, c->field_frag.p,
+                         c->field_hidden, (float *)c->wave[0].f_out.p, c->n_cu, c->stream);
+}
+
+// A scratch slot of `bytes` for a host entry point, filled from `src` if given.
+static int stage(mtx_ctx *c, DevBuf &slot, size_t bytes, const void *src = nullptr) {
+  if (int rc = dalloc(slot, bytes)) return rc;
+  if (src) HIP_TRY(hipMemcpyAsync(slot.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+  return MTX_OK;
+}
+// Copies results back to the host arrays; returns once they have landed.
+struct Unstage {
+  void *dst;
+  const DevBuf &slot;
+  size_t bytes;
+};
+static int unstage(mtx_ctx *c, std::initializer_list<Unstage> outs) {
+  for (const Unstage &o : outs) HIP_TRY(hipMemcpyAsync(o.dst, o.slot.p, o.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MTX_OK;
+}
+
 int mtx_field_features(mtx_ctx *c, uint64_t n, const float *p, const float *wi, uint16_t *feat) {
   int rc = field_check(c, n);
   if (rc) return rc;
@@ -2182,16 +2173,9 @@ int mtx_field_features(mtx_ctx *c, uint64_t n, const float *p, const float *wi, 
   }
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = field_stage_queries(c, n, p, wi))) return rc;
-  if ((rc = dalloc(c->f_feat, 128 * n))) return rc;
-  if ((rc = prim_timer_begin(c))) return rc;
-  mtxd::field_encode(c->field, (const float4 *)c->fq_p.p, (const float4 *)c->fq_d.p, nullptr, (uint32_t)n,
-                     (uint16_t *)c->f_feat.p, c->stream);
-  if ((rc = prim_timer_end(c))) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(feat, c->f_feat.p, 128 * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  prim_timer_read(c);
-  return MTX_OK;
+  if ((rc = dalloc(c->wave[0].f_feat, kFeatBytes * n))) return rc;
+  if ((rc = prim_run(c, [&] { return field_encode_staged(c, n); }))) return rc;
+  return unstage(c, {{feat, c->wave[0].f_feat, kFeatBytes * n}});
 }
 
 int mtx_field_mlp(mtx_ctx *c, uint64_t n, const uint16_t *feat, float *out) {
@@ -2203,18 +2187,10 @@ int mtx_field_mlp(mtx_ctx *c, uint64_t n, const uint16_t *feat, float *out) {
     return MTX_E_ARG;
   }
   HIP_TRY(hipSetDevice(c->device));
-  if ((rc = dalloc(c->f_feat, 128 * n))) return rc;
-  if ((rc = dalloc(c->f_out, 12 * n))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->f_feat.p, feat, 128 * n, hipMemcpyHostToDevice, c->stream));
-  if ((rc = prim_timer_begin(c))) return rc;
-  mtxd::field_mlp((const uint16_t *)c->f_feat.p, nullptr, (uint32_t)n, c->field_frag.p, c->field_hidden,
-                  (float *)c->f_out.p, c->n_cu, c->stream);
-  if ((rc = prim_timer_end(c))) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, c->f_out.p, 12 * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  prim_timer_read(c);
-  return MTX_OK;
+  if ((rc = stage(c, c->wave[0].f_feat, kFeatBytes * n, feat))) return rc;
+  if ((rc = dalloc(c->wave[0].f_out, kOutBytes * n))) return rc;
+  if ((rc = prim_run(c, [&] { return field_mlp_staged(c, n); }))) return rc;
+  return unstage(c, {{out, c->wave[0].f_out, kOutBytes * n}});
 }
 
 int mtx_field_eval(mtx_ctx *c, uint64_t n, const float *p, const float *wi, float *out) {
@@ -2227,314 +2203,248 @@ int mtx_field_eval(mtx_ctx *c, uint64_t n, const float *p, const float *wi, floa
   }
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = field_stage_queries(c, n, p, wi))) return rc;
-  if ((rc = dalloc(c->f_feat, 128 * n))) return rc;
-  if ((rc = dalloc(c->f_out, 12 * n))) return rc;
-  if ((rc = prim_timer_begin(c))) return rc;
-  mtxd::field_encode(c->field, (const float4 *)c->fq_p.p, (const float4 *)c->fq_d.p, nullptr, (uint32_t)n,
-                     (uint16_t *)c->f_feat.p, c->stream);
-  mtxd::field_mlp((const uint16_t *)c->f_feat.p, nullptr, (uint32_t)n, c->field_frag.p, c->field_hidden,
-                  (float *)c->f_out.p, c->n_cu, c->stream);
-  if ((rc = prim_timer_end(c))) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, c->f_out.p, 12 * n, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = dalloc(c->wave[0].f_feat, kFeatBytes * n))) return rc;
+  if ((rc = dalloc(c->wave[0].f_out, kOutBytes * n))) return rc;
+  if ((rc = prim_run(c, [&] {
+         const int e = field_encode_staged(c, n);
+         return e ? e : field_mlp_staged(c, n);
+       })))
+    return rc;
+  return unstage(c, {{out, c->wave[0].f_out, kOutBytes * n}});
+}
+
+// The five primitives, one function each for the host entry (dev = false:
+// host arrays, staged in the scratch slots and copied back) and the _dev
+// entry (device arrays, used in place). `fn` is the entry the caller used.
+// Order: argument and size checks; for device arrays need_device on every
+// pointer before anything touches them, for host arrays the index range
+// loop; workspace and staging; the device-side range check of device
+// indices; the timed launch.
+
+// Host indices: every v[i] < bound.
+static int host_in_range(const char *fn, const char *what, const uint32_t *v, uint64_t n, uint64_t bound) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (v[i] >= bound) {
+      mtx_set_error("%s: %s[%llu] = %u out of range", fn, what, (unsigned long long)i, v[i]);
+      return MTX_E_ARG;
+    }
+  return MTX_OK;
+}
+// Device indices: checked on the device before any kernel indexes with them.
+static int dev_in_range(mtx_ctx *c, const uint32_t *v, uint64_t n, uint32_t bound, uint32_t *bad) {
+  int rc;
+  if ((rc = dalloc(c->s6, 64))) return rc;
+  HIP_TRY(hipMemsetAsync(c->s6.p, 0, 4, c->stream));
+  if ((rc = mtxd::keys_in_range(v, n, bound, (uint32_t *)c->s6.p, c->stream))) return rc;
+  HIP_TRY(hipMemcpyAsync(bad, c->s6.p, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  prim_timer_read(c);
   return MTX_OK;
 }
 
-int mtx_prefix_sum_u32(mtx_ctx *c, const uint32_t *in, uint32_t *out, uint64_t n, int inclusive) {
+static int prefix_sum_u32_impl(mtx_ctx *c, const char *fn, bool dev, const uint32_t *in, uint32_t *out, uint64_t n,
+                               int inclusive) {
   if (!c || (n && (!in || !out))) {
-    mtx_set_error("mtx_prefix_sum_u32: null argument");
+    mtx_set_error("%s: null argument", fn);
     return MTX_E_ARG;
   }
   if (n == 0) return MTX_OK;
   if (n >= (1ull << 32)) {
-    mtx_set_error("mtx_prefix_sum_u32: n >= 2^32");
+    mtx_set_error("%s: n >= 2^32", fn);
     return MTX_E_ARG;
   }
   HIP_TRY(hipSetDevice(c->device));
   int rc;
-  if ((rc = dalloc(c->s0, 4 * n))) return rc;
-  if ((rc = dalloc(c->s1, 4 * n))) return rc;
+  if (dev && (rc = need_device(c, fn, {in, out}))) return rc;
   if ((rc = dalloc(c->s2, mtxd::scan_workspace_bytes(n)))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->s0.p, in, 4 * n, hipMemcpyHostToDevice, c->stream));
-  if ((rc = prim_timer_begin(c))) return rc;
-  rc = mtxd::scan_u32((const uint32_t *)c->s0.p, (uint32_t *)c->s1.p, n, inclusive, c->s2.p, c->stream);
-  if (rc) return rc;
-  if ((rc = prim_timer_end(c))) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, c->s1.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  prim_timer_read(c);
-  return MTX_OK;
+  if (!dev) {
+    if ((rc = stage(c, c->s0, 4 * n, in)) || (rc = stage(c, c->s1, 4 * n))) return rc;
+    in = (const uint32_t *)c->s0.p;
+  }
+  uint32_t *d_out = dev ? out : (uint32_t *)c->s1.p;
+  if ((rc = prim_run(c, [&] { return mtxd::scan_u32(in, d_out, n, inclusive, c->s2.p, c->stream); }))) return rc;
+  return dev ? MTX_OK : unstage(c, {{out, c->s1, 4 * n}});
 }
 
-int mtx_prefix_sum_f32_hs(mtx_ctx *c, const float *in, float *out, uint64_t n) {
+static int prefix_sum_f32_hs_impl(mtx_ctx *c, const char *fn, bool dev, const float *in, float *out, uint64_t n) {
   if (!c || (n && (!in || !out))) {
-    mtx_set_error("mtx_prefix_sum_f32_hs: null argument");
+    mtx_set_error("%s: null argument", fn);
     return MTX_E_ARG;
   }
   if (n == 0) return MTX_OK;
   HIP_TRY(hipSetDevice(c->device));
   int rc;
-  if ((rc = dalloc(c->s0, 4 * n))) return rc;
-  if ((rc = dalloc(c->s1, 4 * n))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->s0.p, in, 4 * n, hipMemcpyHostToDevice, c->stream));
-  float *res = nullptr;
-  if ((rc = prim_timer_begin(c))) return rc;
-  rc = mtxd::scan_f32_hs((float *)c->s0.p, (float *)c->s1.p, n, &res, c->stream);
-  if (rc) return rc;
-  if ((rc = prim_timer_end(c))) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, res, 4 * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  prim_timer_read(c);
-  return MTX_OK;
+  if (dev && (rc = need_device(c, fn, {in, out}))) return rc;
+  if ((rc = dalloc(c->s1, 4 * n))) return rc;  // ping-pong partner of the output
+  if (!dev) {
+    if ((rc = stage(c, c->s0, 4 * n, in)) || (rc = stage(c, c->s2, 4 * n))) return rc;
+    in = (const float *)c->s0.p;
+  }
+  float *d_out = dev ? out : (float *)c->s2.p;
+  if ((rc = prim_run(c, [&] { return mtxd::scan_f32_hs_to(in, d_out, (float *)c->s1.p, n, c->stream); })))
+    return rc;
+  return dev ? MTX_OK : unstage(c, {{out, c->s2, 4 * n}});
 }
 
-int mtx_prefix_sum_u32_dev(mtx_ctx *c, const uint32_t *in, uint32_t *out, uint64_t n, int inclusive) {
-  if (!c || (n && (!in || !out))) {
-    mtx_set_error("mtx_prefix_sum_u32_dev: null argument");
-    return MTX_E_ARG;
-  }
-  if (n == 0) return MTX_OK;
-  if (n >= (1ull << 32)) {
-    mtx_set_error("mtx_prefix_sum_u32_dev: n >= 2^32");
-    return MTX_E_ARG;
-  }
-  HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = need_device(c, "mtx_prefix_sum_u32_dev", {in, out}))) return rc;
-  if ((rc = dalloc(c->s2, mtxd::scan_workspace_bytes(n)))) return rc;
-  if ((rc = prim_timer_begin(c))) return rc;
-  if ((rc = mtxd::scan_u32(in, out, n, inclusive, c->s2.p, c->stream))) return rc;
-  if ((rc = prim_timer_end(c))) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  prim_timer_read(c);
-  return MTX_OK;
-}
-
-int mtx_prefix_sum_f32_hs_dev(mtx_ctx *c, const float *in, float *out, uint64_t n) {
-  if (!c || (n && (!in || !out))) {
-    mtx_set_error("mtx_prefix_sum_f32_hs_dev: null argument");
-    return MTX_E_ARG;
-  }
-  if (n == 0) return MTX_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = need_device(c, "mtx_prefix_sum_f32_hs_dev", {in, out}))) return rc;
-  if ((rc = dalloc(c->s1, 4 * n))) return rc;  // ping-pong partner of out
-  if ((rc = prim_timer_begin(c))) return rc;
-  if ((rc = mtxd::scan_f32_hs_to(in, out, (float *)c->s1.p, n, c->stream))) return rc;
-  if ((rc = prim_timer_end(c))) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  prim_timer_read(c);
-  return MTX_OK;
-}
-
-int mtx_hashgrid_build_dev(mtx_ctx *c, const float *p, uint64_t n, uint32_t resolution, uint32_t n_cells,
-                           uint32_t *cell, uint32_t *cell_size, uint32_t *cell_offset, uint32_t *sample_idx) {
+static int hashgrid_build_impl(mtx_ctx *c, const char *fn, bool dev, const float *p, uint64_t n, uint32_t resolution,
+                               uint32_t n_cells, uint32_t *cell, uint32_t *cell_size, uint32_t *cell_offset,
+                               uint32_t *sample_idx) {
   if (!c || !p || !cell || !cell_size || !cell_offset || !sample_idx || n == 0 || n_cells == 0) {
-    mtx_set_error("mtx_hashgrid_build_dev: bad argument");
+    mtx_set_error("%s: bad argument", fn);
     return MTX_E_ARG;
   }
   if (n >= (1ull << 31)) {
-    mtx_set_error("mtx_hashgrid_build_dev: n too large");
+    mtx_set_error("%s: n too large", fn);
     return MTX_E_ARG;
   }
   HIP_TRY(hipSetDevice(c->device));
   int rc;
-  if ((rc = need_device(c, "mtx_hashgrid_build_dev", {p, cell, cell_size, cell_offset, sample_idx}))) return rc;
+  if (dev && (rc = need_device(c, fn, {p, cell, cell_size, cell_offset, sample_idx}))) return rc;
   if ((rc = dalloc(c->s5, mtxd::hashgrid_workspace_bytes(n, n_cells)))) return rc;
-  if ((rc = prim_timer_begin(c))) return rc;
-  if ((rc = mtxd::hashgrid_build(p, n, resolution, n_cells, cell, cell_size, cell_offset, sample_idx, c->s5.p,
-                                 c->stream)))
+  uint32_t *d_cell = cell, *d_size = cell_size, *d_offset = cell_offset, *d_idx = sample_idx;
+  if (!dev) {
+    if ((rc = stage(c, c->s0, 12 * n, p)) || (rc = stage(c, c->s1, 4 * n)) ||
+        (rc = stage(c, c->s2, 4ull * n_cells)) || (rc = stage(c, c->s3, 4ull * n_cells)) ||
+        (rc = stage(c, c->s4, 4 * n)))
+      return rc;
+    p = (const float *)c->s0.p;
+    d_cell = (uint32_t *)c->s1.p;
+    d_size = (uint32_t *)c->s2.p;
+    d_offset = (uint32_t *)c->s3.p;
+    d_idx = (uint32_t *)c->s4.p;
+  }
+  if ((rc = prim_run(c, [&] {
+         return mtxd::hashgrid_build(p, n, resolution, n_cells, d_cell, d_size, d_offset, d_idx, c->s5.p, c->stream);
+       })))
     return rc;
-  if ((rc = prim_timer_end(c))) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  prim_timer_read(c);
-  return MTX_OK;
+  return dev ? MTX_OK
+             : unstage(c, {{cell, c->s1, 4 * n},
+                           {cell_size, c->s2, 4ull * n_cells},
+                           {cell_offset, c->s3, 4ull * n_cells},
+                           {sample_idx, c->s4, 4 * n}});
+}
+
+static int group_by_u32_impl(mtx_ctx *c, const char *fn, bool dev, const uint32_t *keys, uint64_t n, uint32_t n_keys,
+                             uint32_t *key_size, uint32_t *key_offset, uint32_t *order) {
+  if (!c || !keys || !key_size || !key_offset || !order || n == 0 || n_keys == 0) {
+    mtx_set_error("%s: bad argument", fn);
+    return MTX_E_ARG;
+  }
+  if (n >= (1ull << 31)) {
+    mtx_set_error("%s: n too large", fn);
+    return MTX_E_ARG;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  if (dev ? (rc = need_device(c, fn, {keys, key_size, key_offset, order}))
+          : (rc = host_in_range(fn, "keys", keys, n, n_keys)))
+    return rc;
+  if ((rc = dalloc(c->s5, mtxd::hashgrid_workspace_bytes(n, n_keys)))) return rc;
+  uint32_t *d_size = key_size, *d_offset = key_offset, *d_order = order;
+  if (dev) {
+    uint32_t bad = 0;
+    if ((rc = dev_in_range(c, keys, n, n_keys, &bad))) return rc;
+    if (bad) {
+      mtx_set_error("%s: a key is >= n_keys (%u)", fn, n_keys);
+      return MTX_E_ARG;
+    }
+  } else {
+    if ((rc = stage(c, c->s1, 4 * n, keys)) || (rc = stage(c, c->s2, 4ull * n_keys)) ||
+        (rc = stage(c, c->s3, 4ull * n_keys)) || (rc = stage(c, c->s4, 4 * n)))
+      return rc;
+    keys = (const uint32_t *)c->s1.p;
+    d_size = (uint32_t *)c->s2.p;
+    d_offset = (uint32_t *)c->s3.p;
+    d_order = (uint32_t *)c->s4.p;
+  }
+  if ((rc = prim_run(c, [&] {
+         return mtxd::group_by_u32(keys, n, n_keys, d_size, d_offset, d_order, c->s5.p, c->stream);
+       })))
+    return rc;
+  return dev ? MTX_OK
+             : unstage(c, {{key_size, c->s2, 4ull * n_keys}, {key_offset, c->s3, 4ull * n_keys}, {order, c->s4, 4 * n}});
+}
+
+static int scatter_reduce_f32_impl(mtx_ctx *c, const char *fn, bool dev, int op, float *target, uint64_t n_target,
+                                   const float *value, const uint32_t *index, uint64_t n_value) {
+  if (!c || !target || (n_value && (!value || !index)) || op < 0 || op > 3) {
+    mtx_set_error("%s: bad argument", fn);
+    return MTX_E_ARG;
+  }
+  if (n_value == 0 || n_target == 0) return MTX_OK;
+  if (n_value >= (1ull << 31) || n_target >= (1ull << 31)) {
+    mtx_set_error("%s: size too large", fn);
+    return MTX_E_ARG;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  if (dev ? (rc = need_device(c, fn, {target, value, index}))
+          : (rc = host_in_range(fn, "index", index, n_value, n_target)))
+    return rc;
+  if ((rc = dalloc(c->s3, mtxd::scatter_workspace_bytes(n_target, n_value)))) return rc;
+  float *d_target = target;
+  if (dev) {
+    uint32_t bad = 0;
+    if ((rc = dev_in_range(c, index, n_value, (uint32_t)n_target, &bad))) return rc;
+    if (bad) {
+      mtx_set_error("%s: an index is >= n_target (%llu)", fn, (unsigned long long)n_target);
+      return MTX_E_ARG;
+    }
+  } else {
+    if ((rc = stage(c, c->s0, 4 * n_target, target)) || (rc = stage(c, c->s1, 4 * n_value, value)) ||
+        (rc = stage(c, c->s2, 4 * n_value, index)))
+      return rc;
+    d_target = (float *)c->s0.p;
+    value = (const float *)c->s1.p;
+    index = (const uint32_t *)c->s2.p;
+  }
+  if ((rc = prim_run(c, [&] {
+         return mtxd::scatter_reduce_f32(op, d_target, n_target, value, index, n_value, c->s3.p, c->stream);
+       })))
+    return rc;
+  return dev ? MTX_OK : unstage(c, {{target, c->s0, 4 * n_target}});
+}
+
+int mtx_prefix_sum_u32(mtx_ctx *c, const uint32_t *in, uint32_t *out, uint64_t n, int inclusive) {
+  return prefix_sum_u32_impl(c, "mtx_prefix_sum_u32", false, in, out, n, inclusive);
+}
+int mtx_prefix_sum_u32_dev(mtx_ctx *c, const uint32_t *in, uint32_t *out, uint64_t n, int inclusive) {
+  return prefix_sum_u32_impl(c, "mtx_prefix_sum_u32_dev", true, in, out, n, inclusive);
+}
+
+int mtx_prefix_sum_f32_hs(mtx_ctx *c, const float *in, float *out, uint64_t n) {
+  return prefix_sum_f32_hs_impl(c, "mtx_prefix_sum_f32_hs", false, in, out, n);
+}
+int mtx_prefix_sum_f32_hs_dev(mtx_ctx *c, const float *in, float *out, uint64_t n) {
+  return prefix_sum_f32_hs_impl(c, "mtx_prefix_sum_f32_hs_dev", true, in, out, n);
 }
 
 int mtx_hashgrid_build(mtx_ctx *c, const float *p, uint64_t n, uint32_t resolution, uint32_t n_cells, uint32_t *cell,
                        uint32_t *cell_size, uint32_t *cell_offset, uint32_t *sample_idx) {
-  if (!c || !p || !cell || !cell_size || !cell_offset || !sample_idx || n == 0 || n_cells == 0) {
-    mtx_set_error("mtx_hashgrid_build: bad argument");
-    return MTX_E_ARG;
-  }
-  if (n >= (1ull << 31)) {
-    mtx_set_error("mtx_hashgrid_build: n too large");
-    return MTX_E_ARG;
-  }
-  HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = dalloc(c->s0, 12 * n))) return rc;
-  if ((rc = dalloc(c->s1, 4 * n))) return rc;           // cell
-  if ((rc = dalloc(c->s2, 4 * (size_t)n_cells))) return rc;   // size
-  if ((rc = dalloc(c->s3, 4 * (size_t)n_cells))) return rc;   // offset
-  if ((rc = dalloc(c->s4, 4 * n))) return rc;           // sample_idx
-  if ((rc = dalloc(c->s5, mtxd::hashgrid_workspace_bytes(n, n_cells)))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->s0.p, p, 12 * n, hipMemcpyHostToDevice, c->stream));
-  if ((rc = prim_timer_begin(c))) return rc;
-  rc = mtxd::hashgrid_build((const float *)c->s0.p, n, resolution, n_cells, (uint32_t *)c->s1.p, (uint32_t *)c->s2.p,
-                            (uint32_t *)c->s3.p, (uint32_t *)c->s4.p, c->s5.p, c->stream);
-  if (rc) return rc;
-  if ((rc = prim_timer_end(c))) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(cell, c->s1.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(cell_size, c->s2.p, 4ull * n_cells, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(cell_offset, c->s3.p, 4ull * n_cells, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(sample_idx, c->s4.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  prim_timer_read(c);
-  return MTX_OK;
+  return hashgrid_build_impl(c, "mtx_hashgrid_build", false, p, n, resolution, n_cells, cell, cell_size, cell_offset,
+                             sample_idx);
+}
+int mtx_hashgrid_build_dev(mtx_ctx *c, const float *p, uint64_t n, uint32_t resolution, uint32_t n_cells,
+                           uint32_t *cell, uint32_t *cell_size, uint32_t *cell_offset, uint32_t *sample_idx) {
+  return hashgrid_build_impl(c, "mtx_hashgrid_build_dev", true, p, n, resolution, n_cells, cell, cell_size,
+                             cell_offset, sample_idx);
 }
 
 int mtx_group_by_u32(mtx_ctx *c, const uint32_t *keys, uint64_t n, uint32_t n_keys, uint32_t *key_size,
                      uint32_t *key_offset, uint32_t *order) {
-  if (!c || !keys || !key_size || !key_offset || !order || n == 0 || n_keys == 0) {
-    mtx_set_error("mtx_group_by_u32: bad argument");
-    return MTX_E_ARG;
-  }
-  if (n >= (1ull << 31)) {
-    mtx_set_error("mtx_group_by_u32: n too large");
-    return MTX_E_ARG;
-  }
-  for (uint64_t i = 0; i < n; ++i)
-    if (keys[i] >= n_keys) {
-      mtx_set_error("mtx_group_by_u32: keys[%llu] = %u out of range", (unsigned long long)i, keys[i]);
-      return MTX_E_ARG;
-    }
-  HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = dalloc(c->s1, 4 * n))) return rc;                // keys
-  if ((rc = dalloc(c->s2, 4 * (size_t)n_keys))) return rc;   // size
-  if ((rc = dalloc(c->s3, 4 * (size_t)n_keys))) return rc;   // offset
-  if ((rc = dalloc(c->s4, 4 * n))) return rc;                // order
-  if ((rc = dalloc(c->s5, mtxd::hashgrid_workspace_bytes(n, n_keys)))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->s1.p, keys, 4 * n, hipMemcpyHostToDevice, c->stream));
-  if ((rc = prim_timer_begin(c))) return rc;
-  rc = mtxd::group_by_u32((const uint32_t *)c->s1.p, n, n_keys, (uint32_t *)c->s2.p, (uint32_t *)c->s3.p,
-                          (uint32_t *)c->s4.p, c->s5.p, c->stream);
-  if (rc) return rc;
-  if ((rc = prim_timer_end(c))) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(key_size, c->s2.p, 4ull * n_keys, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(key_offset, c->s3.p, 4ull * n_keys, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(order, c->s4.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  prim_timer_read(c);
-  return MTX_OK;
+  return group_by_u32_impl(c, "mtx_group_by_u32", false, keys, n, n_keys, key_size, key_offset, order);
 }
-
 int mtx_group_by_u32_dev(mtx_ctx *c, const uint32_t *keys, uint64_t n, uint32_t n_keys, uint32_t *key_size,
                          uint32_t *key_offset, uint32_t *order) {
-  if (!c || !keys || !key_size || !key_offset || !order || n == 0 || n_keys == 0) {
-    mtx_set_error("mtx_group_by_u32_dev: bad argument");
-    return MTX_E_ARG;
-  }
-  if (n >= (1ull << 31)) {
-    mtx_set_error("mtx_group_by_u32_dev: n too large");
-    return MTX_E_ARG;
-  }
-  HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = dalloc(c->s5, mtxd::hashgrid_workspace_bytes(n, n_keys)))) return rc;
-  if ((rc = dalloc(c->s6, 64))) return rc;
-  // the keys are device data: range-checked on the device before any
-  // kernel indexes with them
-  HIP_TRY(hipMemsetAsync(c->s6.p, 0, 4, c->stream));
-  mtxd::keys_in_range(keys, n, n_keys, (uint32_t *)c->s6.p, c->stream);
-  uint32_t bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, c->s6.p, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (bad) {
-    mtx_set_error("mtx_group_by_u32_dev: a key is >= n_keys (%u)", n_keys);
-    return MTX_E_ARG;
-  }
-  if ((rc = prim_timer_begin(c))) return rc;
-  rc = mtxd::group_by_u32(keys, n, n_keys, key_size, key_offset, order, c->s5.p, c->stream);
-  if (rc) return rc;
-  if ((rc = prim_timer_end(c))) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  prim_timer_read(c);
-  return MTX_OK;
-}
-
-int mtx_scatter_reduce_f32_dev(mtx_ctx *c, int op, float *target, uint64_t n_target, const float *value,
-                               const uint32_t *index, uint64_t n_value) {
-  if (!c || !target || (n_value && (!value || !index)) || op < 0 || op > 3) {
-    mtx_set_error("mtx_scatter_reduce_f32_dev: bad argument");
-    return MTX_E_ARG;
-  }
-  if (n_value == 0 || n_target == 0) return MTX_OK;
-  if (n_value >= (1ull << 31) || n_target >= (1ull << 31)) {
-    mtx_set_error("mtx_scatter_reduce_f32_dev: size too large");
-    return MTX_E_ARG;
-  }
-  HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = need_device(c, "mtx_scatter_reduce_f32_dev", {target, value, index}))) return rc;
-  if ((rc = dalloc(c->s3, mtxd::scatter_workspace_bytes(n_target, n_value)))) return rc;
-  if ((rc = dalloc(c->s6, 64))) return rc;
-  // the indices are device data: range-checked on the device first
-  HIP_TRY(hipMemsetAsync(c->s6.p, 0, 4, c->stream));
-  mtxd::keys_in_range(index, n_value, (uint32_t)n_target, (uint32_t *)c->s6.p, c->stream);
-  uint32_t bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, c->s6.p, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (bad) {
-    mtx_set_error("mtx_scatter_reduce_f32_dev: an index is >= n_target (%llu)", (unsigned long long)n_target);
-    return MTX_E_ARG;
-  }
-  if ((rc = prim_timer_begin(c))) return rc;
-  if ((rc = mtxd::scatter_reduce_f32(op, target, n_target, value, index, n_value, c->s3.p, c->stream))) return rc;
-  if ((rc = prim_timer_end(c))) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  prim_timer_read(c);
-  return MTX_OK;
+  return group_by_u32_impl(c, "mtx_group_by_u32_dev", true, keys, n, n_keys, key_size, key_offset, order);
 }
 
 int mtx_scatter_reduce_f32(mtx_ctx *c, int op, float *target, uint64_t n_target, const float *value,
                            const uint32_t *index, uint64_t n_value) {
-  if (!c || !target || (n_value && (!value || !index)) || op < 0 || op > 3) {
-    mtx_set_error("mtx_scatter_reduce_f32: bad argument");
-    return MTX_E_ARG;
-  }
-  if (n_value == 0 || n_target == 0) return MTX_OK;
-  if (n_value >= (1ull << 31) || n_target >= (1ull << 31)) {
-    mtx_set_error("mtx_scatter_reduce_f32: size too large");
-    return MTX_E_ARG;
-  }
-  for (uint64_t i = 0; i < n_value; ++i)
-    if (index[i] >= n_target) {
-      mtx_set_error("mtx_scatter_reduce_f32: index[%llu] = %u out of range", (unsigned long long)i, index[i]);
-      return MTX_E_ARG;
-    }
-  HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = dalloc(c->s0, 4 * n_target))) return rc;
-  if ((rc = dalloc(c->s1, 4 * n_value))) return rc;
-  if ((rc = dalloc(c->s2, 4 * n_value))) return rc;
-  if ((rc = dalloc(c->s3, mtxd::scatter_workspace_bytes(n_target, n_value)))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->s0.p, target, 4 * n_target, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->s1.p, value, 4 * n_value, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->s2.p, index, 4 * n_value, hipMemcpyHostToDevice, c->stream));
-  if ((rc = prim_timer_begin(c))) return rc;
-  rc = mtxd::scatter_reduce_f32(op, (float *)c->s0.p, n_target, (const float *)c->s1.p, (const uint32_t *)c->s2.p,
-                                n_value, c->s3.p, c->stream);
-  if (rc) return rc;
-  if ((rc = prim_timer_end(c))) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(target, c->s0.p, 4 * n_target, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  prim_timer_read(c);
-  return MTX_OK;
+  return scatter_reduce_f32_impl(c, "mtx_scatter_reduce_f32", false, op, target, n_target, value, index, n_value);
+}
+int mtx_scatter_reduce_f32_dev(mtx_ctx *c, int op, float *target, uint64_t n_target, const float *value,
+                               const uint32_t *index, uint64_t n_value) {
+  return scatter_reduce_f32_impl(c, "mtx_scatter_reduce_f32_dev", true, op, target, n_target, value, index, n_value);
 }
 
 }  // extern "C"
@@ -2700,10 +2610,11 @@ static int nerad_rhs_dev(mtx_ctx *c, const mtx_nerad_args *a, float *lanes_dev, 
   int rc;
   const uint32_t n = a->batch * a->M;
   const uint32_t bounces = 12;  // first vertex, its BSDF hit, <= 10 next_smooth_si traces (:146)
-  if ((rc = ensure_wavefront(c, n, bounces))) return rc;
-  if ((rc = ensure_cache(c, n))) return rc;
+  Wave &w = c->wave[0];
+  if ((rc = ensure_wave(c, w, n, bounces))) return rc;
+  if ((rc = ensure_cache(c, w, n))) return rc;
   if ((rc = dalloc(c->nr_Lrhs, 12ull * a->batch))) return rc;
-  mtxd::WaveBuffers b = buffers(c);
+  mtxd::WaveBuffers b = views(c, w);
   mtxd::ChunkParams p{};
   p.integrator = MTX_INT_NERAD_RHS;
   p.max_depth = bounces;
@@ -2719,11 +2630,12 @@ static int nerad_rhs_dev(mtx_ctx *c, const mtx_nerad_args *a, float *lanes_dev, 
   mtxd::launch_nerad_raygen(b, p, (const float4 *)c->nr_lhs.p, a->M, c->stream);
   Timer tm{c, st != nullptr};
   uint64_t nt = 0, ns = 0;
-  run_bounces(c, b, p, tm, &nt, &ns);
-  mtxd::field_encode(c->field, b.cq_p, b.cq_d, b.cq_count, n, (uint16_t *)c->f_feat.p, c->stream);
-  mtxd::field_mlp((const uint16_t *)c->f_feat.p, b.cq_count, n, c->field_frag.p, c->field_hidden,
-                  (float *)c->f_out.p, c->n_cu, c->stream);
-  mtxd::launch_nerad_apply(b, (const float *)c->f_out.p, n, 0, c->stream);
+  run_bounces(c, w, b, p, tm, &nt, &ns);
+  if ((rc = mtxd::field_encode(c->field, b.cq_p, b.cq_d, b.cq_count, n, (uint16_t *)w.f_feat.p, c->stream))) return rc;
+  if ((rc = mtxd::field_mlp((const uint16_t *)w.f_feat.p, b.cq_count, n, c->field_frag.p, c->field_hidden,
+                            (float *)w.f_out.p, c->n_cu, c->stream)))
+    return rc;
+  mtxd::launch_nerad_apply(b, (const float *)w.f_out.p, n, 0, c->stream);
   mtxd::launch_nerad_mean(b, a->batch, a->M, (float *)c->nr_Lrhs.p, lanes_dev, c->stream);
   HIP_TRY(hipGetLastError());
   if (queries) HIP_TRY(hipMemcpyAsync(queries, b.cq_count, 4, hipMemcpyDeviceToHost, c->stream));

@@ -166,6 +166,32 @@ def test_dev_entry_points_refuse_host_memory(small_scene):
     out = np.zeros_like(x)
     rc = lib().mtx_prefix_sum_u32_dev(ctx.handle, x.ctypes.data, out.ctypes.data, 10, 1)
     assert rc != 0 and b"not device memory" in lib().mtx_last_error()
+    # every _dev primitive decides this on the host (hipPointerGetAttributes),
+    # before anything that touches the pointers is enqueued
+    f = np.arange(10, dtype=np.float32)
+    fo = np.zeros_like(f)
+    p3 = np.linspace(0.0, 1.0, 30, dtype=np.float32)
+    u = [np.zeros(10, np.uint32) for _ in range(4)]
+    keys = np.arange(10, dtype=np.uint32) % 5
+    L = lib()
+
+    def ptr(a):
+        return a.ctypes.data
+
+
+    calls = {
+        "mtx_prefix_sum_f32_hs_dev": lambda: L.mtx_prefix_sum_f32_hs_dev(ctx.handle, ptr(f), ptr(fo), 10),
+        "mtx_hashgrid_build_dev": lambda: L.mtx_hashgrid_build_dev(ctx.handle, ptr(p3), 10, 4, 10, ptr(u[0]),
+                                                                   ptr(u[1]), ptr(u[2]), ptr(u[3])),
+        "mtx_group_by_u32_dev": lambda: L.mtx_group_by_u32_dev(ctx.handle, ptr(keys), 10, 10, ptr(u[0]), ptr(u[1]),
+                                                               ptr(u[2])),
+        "mtx_scatter_reduce_f32_dev": lambda: L.mtx_scatter_reduce_f32_dev(ctx.handle, 0, ptr(fo), 10, ptr(f),
+                                                                           ptr(keys), 10),
+    }
+    for name, call in calls.items():
+        rc = call()
+        err = L.mtx_last_error()
+        assert rc != 0 and b"not device memory" in err and name.encode() in err, (name, rc, err)
     trace_rays(small_scene, np.zeros((1, 8), np.float32))  # binds the scene
     r = np.zeros((4, 8), np.float32)
     h = np.zeros(16, np.uint32)

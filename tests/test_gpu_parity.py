@@ -151,7 +151,7 @@ def test_render_film_bit_exact(small_scene, oracle, name):
 @pytest.mark.parametrize("name", ["path_test", "mypath", "nrc"])
 def test_two_stream_chunks_bit_exact(small_scene, oracle, name):
     """Renders of >= 2^16 paths alternate their chunks between two wavefronts
-    on two HIP streams (api.cpp Wave2): 7 chunks of 5 rows (boundaries inside
+    on two HIP streams (api.cpp Wave, wave[0] / wave[1]): 7 chunks of 5 rows (boundaries inside
     the sample range of no pixel, an odd count, a short last chunk) give the
     oracle's film bit for bit, as does the default two-chunk split."""
     from mtx import load_dict
@@ -164,6 +164,38 @@ def test_two_stream_chunks_bit_exact(small_scene, oracle, name):
         film = integ.render_film(small_scene, seed=7, spp=spp, chunk_paths=chunk)
         np.testing.assert_array_equal(film, ref, err_msg=f"chunk_paths={chunk}")
     assert ref[..., 3].sum() > 0
+
+
+def test_wave_reuse_across_capacity_changes(small_scene, oracle):
+    """One context, six renders in the order in which stale wavefront state
+    would show: one wave at 4,608 paths; seven chunks over both waves; the
+    default split at 92,160 paths, which grows both waves (a plane offset or a
+    wave-1 view taken before the growth would be stale); the first render
+    again, now in planes sized for ten times its paths; PSSMLT, whose chain
+    planes are laid out by wave 0's capacity, not by the chunk's; a cacheless
+    nrc render below the two-stream threshold. Every film equals the
+    oracle's bit for bit, and the repeated render equals its first run."""
+    from mtx import load_dict
+
+    def check(integ, spp, **kw):
+        film = integ.render_film(small_scene, seed=11, spp=spp, **kw)
+        ref = oracle.render(small_scene, integ.render_args(small_scene, 11, spp))
+        np.testing.assert_array_equal(film, ref, err_msg=f"{integ.__class__.__name__} spp={spp} {kw}")
+        return film
+
+    path = load_dict({"type": "path_test", "max_depth": 6})
+    first = check(path, 2)
+    check(path, 32, chunk_paths=64 * 5 * 32)
+    check(path, 40)
+    again = check(path, 2)
+    np.testing.assert_array_equal(again, first)
+    assert first[..., 3].sum() > 0
+    iterations = 45  # past the bootstrap: iterations 41..44 splat
+    mlt = load_dict({"type": "pssmlt", "iterations": iterations})
+    film = mlt.render_film(small_scene, seed=11, spp=1)
+    np.testing.assert_array_equal(film, oracle.pssmlt_render(small_scene, mlt.render_args(small_scene, 11, 1), iterations))
+    assert film[..., 3].sum() > 0
+    check(load_dict({"type": "nrc"}), 4)
 
 
 def test_rank_shards_and_row_bands(small_scene, oracle):
