@@ -97,6 +97,9 @@ typedef struct mtx_texture {
  * mesh_sum = cdf[mesh_count - 1], mesh_norm = 1 / mesh_sum, mesh_kind =
  * MTX_EMITTER_MESH, inv_area = 1 / (sum of the triangle areas). The shape
  * that carries a mesh emitter is shaded with face normals (flag bit 0).
+ * mtx_scene_update_vertices rebuilds pmf, cdf and the five words valid_lo,
+ * valid_hi, sum, norm and inv_area from moved vertices; offset, count, kind,
+ * radiance and the prim block stay.
  * mtx_scene_upload refuses (MTX_E_ARG) a mesh record whose table range leaves
  * `tables`, whose entries are not exactly the triangles of the shapes that
  * name the emitter, whose cdf decreases, or whose sum is not positive. */
@@ -387,11 +390,30 @@ int mtx_scene_upload(mtx_ctx *ctx, const mtx_scene_desc *scene);
  * child boxes and the environment's bounding sphere are rewritten in place on
  * the context's stream, complete on return, and equal what mtx_bvh_refit /
  * mtx_bvh_refit_occlusion and a fresh upload would give, bit for bit. Device
- * pointers of the scene do not move. A read-only pre-pass refuses
- * (MTX_E_ARG, scene untouched) a wrong vertex count, a non-finite coordinate
- * or one of magnitude above 2^37, and any change to a triangle of an emitter
- * shape (area emitters are held analytically in the emitter records; moving their
- * triangles would split emitter sampling from traversal). Neural-radiosity
+ * pointers of the scene do not move.
+ *   Mesh emitters move with their vertices. For each one, in `tables`:
+ * pmf[k] becomes the fp32 area of entry k's triangle at the new positions
+ * (mtx_core/discrete.h tri_area, mtx_tri_area_f32), cdf[k] the inclusive
+ * prefix accumulated sequentially in double, in entry order, and stored as
+ * float; the prim block stays. In the record mesh_valid_lo / _hi become the
+ * first / last entry with pmf > 0, mesh_sum = cdf[n - 1], mesh_norm = inv_area
+ * = 1.f / mesh_sum (one fp32 division); the other words stay. So unchanged
+ * vertices give back the uploaded tables, and the result equals a fresh upload
+ * of the scene a loader builds from the new vertices in this leaf order, bit
+ * for bit. The device scans in parallel only where the order provably cannot
+ * matter: with M = ilogb(largest area), m = max(ilogb(smallest non-zero
+ * area), -126) - 23 and n entries, M + 1 + ceil(log2 n) - m <= 53 makes every
+ * partial sum of every subset a double, so no addition rounds
+ * (prefix_order_free); an emitter that fails this is summed by one lane in
+ * entry order (slow, exact).
+ *   A read-only pre-pass refuses (MTX_E_ARG, scene untouched) a wrong vertex
+ * count, a non-finite coordinate or one of magnitude above 2^37, a mesh
+ * emitter whose triangles have no finite positive total area at the new
+ * positions (all collapsed, or an area that overflows fp32; the message names
+ * the emitter), and any change to a triangle of a rectangle-emitter shape: a
+ * rectangle emitter is an analytic record derived from to_world, not from its
+ * vertices, and four moved vertices cannot give back the loader's bits, so
+ * moving its triangles would split emitter sampling from traversal. Neural-radiosity
  * surface tables are dropped as by an upload. ReSTIR GI reservoirs are kept:
  * the reference has no reprojection under moving geometry either, so a caller
  * restarts with frame = 0 or accepts stale reuse. Should a refit pass fail
@@ -403,8 +425,14 @@ int mtx_scene_update_vertices(mtx_ctx *ctx, const float *vpos, const float *vnor
  * which = 0 nodes, 1 occ_nodes (the ABI's words), 2 the closest-hit tree's
  * triangles and 3 the occlusion tree's (9 floats each: v0, e1, e2), 4 the
  * shading records (32 floats per triangle), 5 vpos, 6 vnormal, 7 the
- * environment's bounding sphere (centre.xyz, radius). n_bytes must match. */
+ * environment's bounding sphere (centre.xyz, radius), 8 the float `tables`
+ * (n_tables floats), 9 the emitter records (64 bytes each). n_bytes must
+ * match. */
 int mtx_scene_read(mtx_ctx *ctx, int which, void *out, uint64_t n_bytes);
+/* area_out[i] = the fp32 area of triangle i of tris (9 floats each: p0, p1,
+ * p2), in the arithmetic of a mesh emitter's pmf (mtx_core/discrete.h
+ * tri_area): what mtx_scene_update_vertices computes on the device. Host. */
+int mtx_tri_area_f32(const float *tris, uint64_t n, float *area_out);
 
 /* --------------------------- integrators -------------------------- */
 /* Render film rows [y0,y1) plus the border b of args->rfilter into

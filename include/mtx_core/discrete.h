@@ -72,6 +72,29 @@ MTX_HD uint32_t discrete_sample_reuse_fixed(const DiscreteDist &d, float u, floa
   return i;
 }
 
+// The pmf entry of a mesh emitter's triangle: Mesh::face_area, half the norm
+// of the edge cross product in fp32. The loader (scene.py _tri_area_f32) and
+// the device's table rebuild (refit.hip) both follow this sequence.
+MTX_HD float tri_area(V3 p0, V3 p1, V3 p2) { return norm(cross(p1 - p0, p2 - p0)) * 0.5f; }
+
+// When the order of a double-precision prefix sum over n fp32 areas cannot
+// matter. max_bits / min_bits: the bit patterns of the largest area and of the
+// smallest non-zero one (both finite and positive). With M = ilogb(largest)
+// (a denormal counts as -126, which only enlarges the bound) and m =
+// max(ilogb(smallest), -126) - 23 the exponent of the smallest area's last
+// mantissa bit, every area is a multiple of 2^m (a larger fp32 value has a
+// last bit at least as high) and below 2^(M+1), so every partial sum of every
+// subset is a non-negative multiple of 2^m below n 2^(M+1) <=
+// 2^(M+1+ceil(log2 n)). Such a number has at most M + 1 + ceil(log2 n) - m
+// significant bits; if that is <= 53 it is a double, no addition in any
+// association rounds, and every scan order gives the sequential result.
+MTX_HD bool prefix_order_free(uint32_t max_bits, uint32_t min_bits, uint32_t n) {
+  const int eM = (int)(max_bits >> 23), em = (int)(min_bits >> 23);
+  const int M = (eM > 1 ? eM : 1) - 127, m = (em > 1 ? em : 1) - 127 - 23;
+  const int lg = n > 1 ? 32 - __builtin_clz(n - 1) : 0;
+  return M + 1 + lg - m <= 53;
+}
+
 MTX_HD V2 square_to_uniform_triangle(V2 s) {
   const float t = safe_sqrt(1.f - s.x);
   return V2{1.f - t, t * s.y};

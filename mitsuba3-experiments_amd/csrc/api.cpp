@@ -178,7 +178,10 @@ struct mtx_ctx {
   // first update, not by upload.
   DevBuf occ_perm, lvl4_list, lvl8_list, rf_state, rf_tbox, rf_nbox, rf_vpos, rf_vnormal;
   std::vector<uint32_t> lvl4_first, lvl8_first;
-  uint32_t scene_n_nodes = 0, scene_n_occ = 0, scene_n_verts = 0;
+  uint32_t scene_n_nodes = 0, scene_n_occ = 0, scene_n_verts = 0, scene_n_tables = 0;
+  // mesh emitter tables of a vertex update (refit.h EmTables): lists and scratch, sized at upload
+  DevBuf em_slots, em_blocks, em_state, em_pmf, em_cdf, em_bsum, em_bstat;
+  mtxd::EmTables em_tables = {};
   // shared by both wavefronts
   DevBuf stats;
   DevBuf rs_heads;  // per-XCD claim cursors of k_trace_test
@@ -675,6 +678,46 @@ int mtx_scene_upload(mtx_ctx *c, const mtx_scene_desc *d) {
   if ((rc = upload(c->textures, d->textures, d->n_textures, st))) return rc;
   if ((rc = upload(c->texels, d->texels, d->n_texels, st))) return rc;
   if ((rc = upload(c->tables, d->tables, d->n_tables, st))) return rc;
+  c->scene_n_tables = d->n_tables;
+  {
+    // what a vertex update needs to rebuild the mesh emitters' tables
+    std::vector<mtxd::EmSlot> slots;
+    std::vector<mtxd::EmBlock> blks;
+    uint64_t flat = 0;
+    for (uint32_t i = 0; i < d->n_emitters; ++i) {
+      const mtx_emitter &e = d->emitters[i];
+      if (!(e.normal[0] == 0.f && e.normal[1] == 0.f && e.normal[2] == 0.f)) continue;  // a rectangle
+      mtxd::EmSlot sl = {};
+      sl.emitter = i;
+      sl.offset = e.mesh_offset;
+      sl.count = e.mesh_count;
+      sl.flat = (uint32_t)flat;
+      sl.block = (uint32_t)blks.size();
+      for (uint64_t first = 0; first < e.mesh_count; first += mtxd::kEmBlock)
+        blks.push_back({(uint32_t)slots.size(), (uint32_t)first});
+      slots.push_back(sl);
+      flat += e.mesh_count;  // <= n_tris: every triangle is listed at most once (check_mesh_emitters)
+    }
+    mtxd::EmTables &t = c->em_tables;
+    t = {};
+    t.n_slots = (uint32_t)slots.size();
+    t.n_blocks = (uint32_t)blks.size();
+    if ((rc = upload(c->em_slots, slots.data(), slots.size(), st))) return rc;
+    if ((rc = upload(c->em_blocks, blks.data(), blks.size(), st))) return rc;
+    if ((rc = dalloc(c->em_state, 4ull * mtxd::EM_WORDS * slots.size()))) return rc;
+    if ((rc = dalloc(c->em_pmf, 4ull * flat))) return rc;
+    if ((rc = dalloc(c->em_cdf, 4ull * flat))) return rc;
+    if ((rc = dalloc(c->em_bsum, 8ull * blks.size()))) return rc;
+    if ((rc = dalloc(c->em_bstat, 16ull * blks.size()))) return rc;
+    HIP_TRY(hipStreamSynchronize(st));  // slots and blks are freed at scope exit
+    t.slots = (const mtxd::EmSlot *)c->em_slots.p;
+    t.blocks = (const mtxd::EmBlock *)c->em_blocks.p;
+    t.state = (uint32_t *)c->em_state.p;
+    t.pmf = (float *)c->em_pmf.p;
+    t.cdf = (float *)c->em_cdf.p;
+    t.bsum = (double *)c->em_bsum.p;
+    t.bstat = (uint32_t *)c->em_bstat.p;
+  }
   {
     // per-triangle shading records (compute_si_dev)
     std::vector<float> rec(32 * (size_t)d->n_tris, 0.f);
@@ -1740,9 +1783,11 @@ static int need_device(const mtx_ctx *c, const char *fn, std::initializer_list<c
 }
 
 // New vertex positions for the uploaded scene (refit.hip). The pre-pass reads
-// only; a refusal leaves the scene as it was. After it every pass is
-// stream-ordered: triangles, the closest-hit tree's levels from the deepest
-// to the root, the occlusion records, the occlusion tree's levels.
+// only -- the mesh emitters' new tables go to scratch -- and a refusal leaves
+// the scene as it was. After it every pass is stream-ordered: triangles, the
+// mesh emitters' tables and records from the scratch, the closest-hit tree's
+// levels from the deepest to the root, the occlusion records, the occlusion
+// tree's levels.
 int mtx_scene_update_vertices(mtx_ctx *c, const float *vpos, const float *vnormal, uint32_t n_verts, int dev) {
   if (!c || !vpos) {
     mtx_set_error("mtx_scene_update_vertices: null argument");
@@ -1784,7 +1829,9 @@ int mtx_scene_update_vertices(mtx_ctx *c, const float *vpos, const float *vnorma
   }
   uint32_t *state = (uint32_t *)c->rf_state.p;
   mtxd::refit_state_init(state, st);
-  mtxd::refit_prepass(vp, n_verts, s.tri_vidx, s.tri_shape, s.shapes, (const float *)c->shade_rec.p, n_tris, state, st);
+  mtxd::refit_prepass(vp, n_verts, s.tri_vidx, s.tri_shape, s.shapes, s.emitters, (const float *)c->shade_rec.p,
+                      n_tris, state, st);
+  mtxd::refit_emitter_tables(c->em_tables, vp, s.tri_vidx, s.tables, state, st);
   uint32_t h[mtxd::RF_WORDS];
   HIP_TRY(hipMemcpyAsync(h, state, sizeof(h), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -1795,9 +1842,14 @@ int mtx_scene_update_vertices(mtx_ctx *c, const float *vpos, const float *vnorma
     return MTX_E_ARG;
   }
   if (h[mtxd::RF_FLAGS] & mtxd::RF_BAD_EMITTER) {
-    mtx_set_error("mtx_scene_update_vertices: a vertex of an emitter shape would move (a rectangle emitter is "
-                  "held analytically and a mesh emitter's triangle distribution is built at load time; neither can "
-                  "be animated); the scene is unchanged");
+    mtx_set_error("mtx_scene_update_vertices: a vertex of a rectangle emitter shape would move (a rectangle "
+                  "emitter is an analytic record derived from to_world, not from its vertices, and cannot be "
+                  "animated; mesh emitters can); the scene is unchanged");
+    return MTX_E_ARG;
+  }
+  if (h[mtxd::RF_FLAGS] & mtxd::RF_BAD_AREA) {
+    mtx_set_error("mtx_scene_update_vertices: mesh emitter %u: its triangles have no finite positive area at the new "
+                  "positions; the scene is unchanged", h[mtxd::RF_EM]);
     return MTX_E_ARG;
   }
   // from here on the scene is written
@@ -1807,6 +1859,7 @@ int mtx_scene_update_vertices(mtx_ctx *c, const float *vpos, const float *vnorma
     HIP_TRY(hipMemcpyAsync(c->vnormal.p, vn, vbytes, hipMemcpyDeviceToDevice, st));
   float *tbox = (float *)c->rf_tbox.p, *nbox = (float *)c->rf_nbox.p;
   mtxd::refit_triangles(vp, vn, s.tri_vidx, n_tris, (float *)c->tri.p, (float *)c->shade_rec.p, tbox, st);
+  mtxd::refit_emitter_commit(c->em_tables, (float *)c->tables.p, (mtx_emitter *)c->emitters.p, st);
   const float extent = mtx::u2f(h[mtxd::RF_EXTENT]), occ_extent = mtx::u2f(h[mtxd::RF_OCC_EXTENT]);
   for (size_t l = c->lvl4_first.size() - 1; l-- > 0;)
     mtxd::refit_level4((int32_t *)c->nodes.p, c->lvl4_first[l], c->lvl4_first[l + 1] - c->lvl4_first[l],
@@ -1865,8 +1918,10 @@ int mtx_scene_read(mtx_ctx *c, int which, void *out, uint64_t n_bytes) {
     case 5: src = c->vpos.p; need = 12 * nv; break;
     case 6: src = c->vnormal.p; need = c->vnormal.p ? 12 * nv : 0; break;
     case 7: need = 16; break;
+    case 8: src = c->tables.p; need = 4ull * c->scene_n_tables; break;
+    case 9: src = c->emitters.p; need = sizeof(mtx_emitter) * (uint64_t)c->scene.n_emitters; break;
     default:
-      mtx_set_error("mtx_scene_read: which=%d not in 0..7", which);
+      mtx_set_error("mtx_scene_read: which=%d not in 0..9", which);
       return MTX_E_ARG;
   }
   if (n_bytes != need) {

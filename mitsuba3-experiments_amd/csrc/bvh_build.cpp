@@ -26,6 +26,7 @@
 
 #include "mtx.h"
 #include "mtx_core/bsdf.h"
+#include "mtx_core/discrete.h"
 #include "mtx_core/geometry.h"
 #include "mtx_core/microfacet.h"
 #include "mtx_core/refit.h"
@@ -922,6 +923,19 @@ extern "C" int mtx_bvh_refit_occlusion(const float *tri_geom, const uint32_t *oc
   if (!ok) {  // cannot happen within the magnitude bound (geometry.h)
     mtx_set_error("mtx_bvh_refit_occlusion: child box quantisation failed");
     return MTX_E_ARG;
+  }
+  return MTX_OK;
+}
+
+// mtx::tri_area on the host: the pmf entry a vertex update writes on the device.
+extern "C" int mtx_tri_area_f32(const float *tris, uint64_t n, float *area_out) {
+  if (n && (!tris || !area_out)) {
+    mtx_set_error("mtx_tri_area_f32: null argument");
+    return MTX_E_ARG;
+  }
+  for (uint64_t i = 0; i < n; ++i) {
+    const float *p = tris + 9 * i;
+    area_out[i] = mtx::tri_area(mtx::v3(p[0], p[1], p[2]), mtx::v3(p[3], p[4], p[5]), mtx::v3(p[6], p[7], p[8]));
   }
   return MTX_OK;
 }

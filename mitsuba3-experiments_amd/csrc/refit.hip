@@ -11,8 +11,36 @@
 // writes its own. One thread per node: the per-child loop keeps the shared
 // host/device code in one piece; the passes are bound by the triangle pass's
 // traffic, not by the levels.
+//
+// Mesh emitters move with their vertices: their tables in `tables` (mtx.h:
+// pmf the fp32 triangle areas, cdf the inclusive prefix accumulated
+// sequentially in double, in entry order, and stored as float) are rebuilt in
+// the pre-pass into scratch and committed once every check has passed.
+//   areas  one thread per entry: prim -> tri_vidx -> the new vpos ->
+//          mtx::tri_area; per block (wave reductions, no atomics: the blocks
+//          of a large light would all meet on four words) the bits of the
+//          largest and of the smallest non-zero area, the first / last entry
+//          with pmf > 0 and the double sum of its areas.
+//   reduce one block per emitter folds its blocks' four words (min and max:
+//          any order).
+//   scan   A parallel scan adds in another order than the definition, so it
+//          runs only where the order provably cannot matter
+//          (mtx::prefix_order_free, mtx_core/discrete.h): with M = ilogb of
+//          the largest area, m = max(ilogb(smallest non-zero area), -126) - 23
+//          and n entries, every partial sum of every subset of the areas is a
+//          non-negative multiple of 2^m below 2^(M + 1 + ceil(log2 n)); if
+//          M + 1 + ceil(log2 n) - m <= 53 each such sum is a double, no
+//          addition in any association rounds, and the block sums, the wave
+//          scans and their offsets all equal the sequential prefix. An
+//          emitter that fails the predicate takes the ordered fallback: one
+//          wave stages 1024 entries at a time through LDS and lane 0 adds
+//          them in entry order. Slow, and exactly the definition.
+//   finish sum = cdf[n - 1], norm = 1 / sum (one fp32 division); no entry
+//          with pmf > 0, a non-finite area, or a sum or norm that is not
+//          finite and positive is RF_BAD_AREA.
 #include "refit.h"
 
+#include "mtx_core/discrete.h"
 #include "mtx_core/refit.h"
 
 namespace mtxd {
@@ -48,7 +76,7 @@ __device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
 
 __global__ void k_refit_state_init(uint32_t *state) {
   const uint32_t i = threadIdx.x;
-  if (i < RF_WORDS) state[i] = (i >= RF_LO && i < RF_LO + 3) ? 0xffffffffu : 0u;
+  if (i < RF_WORDS) state[i] = ((i >= RF_LO && i < RF_LO + 3) || i == RF_EM) ? 0xffffffffu : 0u;
 }
 
 // All vertices: finite and within the bound; their box (the environment's
@@ -79,12 +107,14 @@ __global__ __launch_bounds__(kBlock) void k_refit_verts(const float *__restrict_
 }
 
 // Leaf-order triangles: the two extents, the occlusion points' bound, and
-// that no triangle of an emitter shape moves (its vertices against the
-// position rows of its shading record).
+// that no triangle of a rectangle-emitter shape moves (its vertices against
+// the position rows of its shading record; the record of a rectangle emitter
+// has a non-zero normal, mtx.h).
 __global__ __launch_bounds__(kBlock) void k_refit_check_tris(const float *__restrict__ vpos,
                                                              const uint32_t *__restrict__ tri_vidx,
                                                              const uint32_t *__restrict__ tri_shape,
                                                              const mtx_shape *__restrict__ shapes,
+                                                             const mtx_emitter *__restrict__ emitters,
                                                              const float *__restrict__ shade_rec, uint32_t n_tris,
                                                              uint32_t *state) {
   const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
@@ -107,7 +137,8 @@ __global__ __launch_bounds__(kBlock) void k_refit_check_tris(const float *__rest
       const uint32_t b = mtx::abs_bits(pts[j]);
       occ_ext = b > occ_ext ? b : occ_ext;
     }
-    if (shapes[tri_shape[t]].emitter >= 0) {
+    const int32_t em = shapes[tri_shape[t]].emitter;
+    if (em >= 0 && !(emitters[em].normal[0] == 0.f && emitters[em].normal[1] == 0.f && emitters[em].normal[2] == 0.f)) {
       const float *r = shade_rec + 32 * (size_t)t;
       for (int k = 0; k < 3; ++k)
         for (int a = 0; a < 3; ++a)
@@ -203,6 +234,186 @@ __global__ __launch_bounds__(kBlock) void k_refit_level8(uint32_t *nodes, uint32
   if (!ok) atomicOr(&state[RF_FLAGS], (uint32_t)RF_BAD_QUANT);
 }
 
+// ------------------------------------------------- mesh emitter tables --
+static_assert(kEmBlock == 256, "four waves per block below");
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// 1: block-parallel scan, 2: ordered fallback, 0: refused (no scan).
+__device__ __forceinline__ uint32_t em_path(const uint32_t *st, uint32_t n) {
+  if (st[EM_MAX] >= 0x7f800000u || st[EM_LO] == 0xffffffffu) return 0u;
+  return mtx::prefix_order_free(st[EM_MAX], st[EM_MIN], n) ? 1u : 2u;
+}
+
+__global__ __launch_bounds__(kEmBlock) void k_em_areas(EmTables t, const float *__restrict__ vpos,
+                                                       const uint32_t *__restrict__ tri_vidx,
+                                                       const float *__restrict__ tables) {
+  __shared__ double wsum[4];
+  __shared__ uint32_t wst[4][4];
+  const EmBlock b = t.blocks[blockIdx.x];
+  const EmSlot s = t.slots[b.slot];
+  const uint32_t k = b.first + threadIdx.x;
+  const bool in = k < s.count;
+  float a = 0.f;
+  if (in) {
+    const uint32_t prim = mtx::f2u(tables[(size_t)s.offset + 2 * (size_t)s.count + k]);
+    mtx::V3 p[3];
+    for (int j = 0; j < 3; ++j) {
+      const uint32_t vi = tri_vidx[3 * (size_t)prim + j];
+      p[j] = mtx::v3(vpos[3 * (size_t)vi], vpos[3 * (size_t)vi + 1], vpos[3 * (size_t)vi + 2]);
+    }
+    a = mtx::tri_area(p[0], p[1], p[2]);
+    t.pmf[(size_t)s.flat + k] = a;
+  }
+  const bool pos = in && a > 0.f;
+  const uint32_t mx = wave_max_u32(in ? mtx::f2u(a) : 0u), mn = wave_min_u32(pos ? mtx::f2u(a) : 0xffffffffu);
+  const uint32_t lo = wave_min_u32(pos ? k : 0xffffffffu), hi = wave_max_u32(pos ? k : 0u);
+  const double ws = wave_sum_f64(in ? (double)a : 0.0);
+  if ((threadIdx.x & 63) == 0) {
+    uint32_t *w = wst[threadIdx.x >> 6];
+    w[EM_MAX] = mx;
+    w[EM_MIN] = mn;
+    w[EM_LO] = lo;
+    w[EM_HI] = hi;
+    wsum[threadIdx.x >> 6] = ws;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    t.bsum[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    uint32_t *o = t.bstat + 4 * (size_t)blockIdx.x;
+    o[EM_MAX] = max(max(wst[0][EM_MAX], wst[1][EM_MAX]), max(wst[2][EM_MAX], wst[3][EM_MAX]));
+    o[EM_MIN] = min(min(wst[0][EM_MIN], wst[1][EM_MIN]), min(wst[2][EM_MIN], wst[3][EM_MIN]));
+    o[EM_LO] = min(min(wst[0][EM_LO], wst[1][EM_LO]), min(wst[2][EM_LO], wst[3][EM_LO]));
+    o[EM_HI] = max(max(wst[0][EM_HI], wst[1][EM_HI]), max(wst[2][EM_HI], wst[3][EM_HI]));
+  }
+}
+
+// One block per emitter: its blocks' words into its state.
+__global__ __launch_bounds__(kEmBlock) void k_em_reduce(EmTables t) {
+  __shared__ uint32_t wst[4][4];
+  const EmSlot s = t.slots[blockIdx.x];
+  const uint32_t nb = (s.count + kEmBlock - 1) / kEmBlock;
+  uint32_t mx = 0u, mn = 0xffffffffu, lo = 0xffffffffu, hi = 0u;
+  for (uint32_t i = threadIdx.x; i < nb; i += kEmBlock) {
+    const uint32_t *b = t.bstat + 4 * (size_t)(s.block + i);
+    mx = max(mx, b[EM_MAX]);
+    mn = min(mn, b[EM_MIN]);
+    lo = min(lo, b[EM_LO]);
+    hi = max(hi, b[EM_HI]);
+  }
+  mx = wave_max_u32(mx);
+  mn = wave_min_u32(mn);
+  lo = wave_min_u32(lo);
+  hi = wave_max_u32(hi);
+  if ((threadIdx.x & 63) == 0) {
+    uint32_t *w = wst[threadIdx.x >> 6];
+    w[EM_MAX] = mx;
+    w[EM_MIN] = mn;
+    w[EM_LO] = lo;
+    w[EM_HI] = hi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t *st = t.state + EM_WORDS * (size_t)blockIdx.x;
+    st[EM_MAX] = max(max(wst[0][EM_MAX], wst[1][EM_MAX]), max(wst[2][EM_MAX], wst[3][EM_MAX]));
+    st[EM_MIN] = min(min(wst[0][EM_MIN], wst[1][EM_MIN]), min(wst[2][EM_MIN], wst[3][EM_MIN]));
+    st[EM_LO] = min(min(wst[0][EM_LO], wst[1][EM_LO]), min(wst[2][EM_LO], wst[3][EM_LO]));
+    st[EM_HI] = max(max(wst[0][EM_HI], wst[1][EM_HI]), max(wst[2][EM_HI], wst[3][EM_HI]));
+  }
+}
+
+// Emitters that satisfy mtx::prefix_order_free: every sum below is exact, so
+// its order is free (the header comment).
+__global__ __launch_bounds__(kEmBlock) void k_em_scan(EmTables t) {
+  __shared__ double woff[4], wtot[4];
+  const EmBlock b = t.blocks[blockIdx.x];
+  const EmSlot s = t.slots[b.slot];
+  if (em_path(t.state + EM_WORDS * (size_t)b.slot, s.count) != 1u) return;  // the whole block
+  const uint32_t before = b.first / kEmBlock, base = blockIdx.x - before;  // this emitter's earlier blocks
+  double off = 0.0;
+  for (uint32_t i = threadIdx.x; i < before; i += kEmBlock) off += t.bsum[base + i];
+  off = wave_sum_f64(off);
+  const uint32_t k = b.first + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const bool in = k < s.count;
+  double v = in ? (double)t.pmf[(size_t)s.flat + k] : 0.0;
+  for (int o = 1; o < 64; o <<= 1) {
+    const double w = __shfl_up(v, o, 64);
+    if ((int)lane >= o) v += w;
+  }
+  if (lane == 0) woff[wv] = off;
+  if (lane == 63) wtot[wv] = v;
+  __syncthreads();
+  double add = ((woff[0] + woff[1]) + woff[2]) + woff[3];
+  for (uint32_t w = 0; w < wv; ++w) add += wtot[w];
+  if (in) t.cdf[(size_t)s.flat + k] = (float)(add + v);
+}
+
+// The others: the definition itself. One wave per emitter; lane 0 adds in
+// entry order, the wave moves the data.
+__global__ __launch_bounds__(64) void k_em_scan_ordered(EmTables t) {
+  constexpr uint32_t kChunk = 1024;
+  __shared__ float buf[kChunk];
+  const EmSlot s = t.slots[blockIdx.x];
+  if (em_path(t.state + EM_WORDS * (size_t)blockIdx.x, s.count) != 2u) return;
+  double acc = 0.0;  // lane 0's
+  for (uint32_t c = 0; c < s.count; c += kChunk) {
+    const uint32_t m = s.count - c < kChunk ? s.count - c : kChunk;
+    for (uint32_t i = threadIdx.x; i < m; i += 64) buf[i] = t.pmf[(size_t)s.flat + c + i];
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (uint32_t i = 0; i < m; ++i) {
+        acc += (double)buf[i];
+        buf[i] = (float)acc;
+      }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < m; i += 64) t.cdf[(size_t)s.flat + c + i] = buf[i];
+    __syncthreads();
+  }
+}
+
+__global__ void k_em_finish(EmTables t, uint32_t *state) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= t.n_slots) return;
+  const EmSlot s = t.slots[i];
+  uint32_t *st = t.state + EM_WORDS * (size_t)i;
+  const uint32_t path = em_path(st, s.count);
+  bool ok = path != 0u;
+  if (ok) {
+    const float sum = t.cdf[(size_t)s.flat + s.count - 1], norm = 1.f / sum;
+    ok = sum > 0.f && mtx::isfinite_(sum) && norm > 0.f && mtx::isfinite_(norm);
+    st[EM_SUM] = mtx::f2u(sum);
+    st[EM_NORM] = mtx::f2u(norm);
+  }
+  st[EM_PATH] = ok ? path : 0u;
+  if (!ok) {
+    atomicOr(&state[RF_FLAGS], (uint32_t)RF_BAD_AREA);
+    atomicMin(&state[RF_EM], s.emitter);
+  }
+}
+
+__global__ __launch_bounds__(kEmBlock) void k_em_commit(EmTables t, float *__restrict__ tables,
+                                                        mtx_emitter *__restrict__ emitters) {
+  const EmBlock b = t.blocks[blockIdx.x];
+  const EmSlot s = t.slots[b.slot];
+  const uint32_t k = b.first + threadIdx.x;
+  if (k < s.count) {
+    tables[(size_t)s.offset + k] = t.pmf[(size_t)s.flat + k];
+    tables[(size_t)s.offset + s.count + k] = t.cdf[(size_t)s.flat + k];
+  }
+  if (k == 0) {
+    const uint32_t *st = t.state + EM_WORDS * (size_t)b.slot;
+    mtx_emitter &e = emitters[s.emitter];
+    e.mesh_valid_lo = st[EM_LO];
+    e.mesh_valid_hi = st[EM_HI];
+    e.mesh_sum = mtx::u2f(st[EM_SUM]);
+    e.mesh_norm = mtx::u2f(st[EM_NORM]);
+    e.inv_area = mtx::u2f(st[EM_NORM]);
+  }
+}
+
 inline unsigned blocks(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 
 }  // namespace
@@ -212,10 +423,26 @@ float refit_key_decode(uint32_t key) { return mtx::u2f((key & 0x80000000u) ? (ke
 void refit_state_init(uint32_t *state, hipStream_t st) { hipLaunchKernelGGL(k_refit_state_init, 1, 64, 0, st, state); }
 
 void refit_prepass(const float *vpos, uint32_t n_verts, const uint32_t *tri_vidx, const uint32_t *tri_shape,
-                   const mtx_shape *shapes, const float *shade_rec, uint32_t n_tris, uint32_t *state, hipStream_t st) {
+                   const mtx_shape *shapes, const mtx_emitter *emitters, const float *shade_rec, uint32_t n_tris,
+                   uint32_t *state, hipStream_t st) {
   hipLaunchKernelGGL(k_refit_verts, blocks(n_verts), kBlock, 0, st, vpos, n_verts, state);
-  hipLaunchKernelGGL(k_refit_check_tris, blocks(n_tris), kBlock, 0, st, vpos, tri_vidx, tri_shape, shapes, shade_rec,
-                     n_tris, state);
+  hipLaunchKernelGGL(k_refit_check_tris, blocks(n_tris), kBlock, 0, st, vpos, tri_vidx, tri_shape, shapes, emitters,
+                     shade_rec, n_tris, state);
+}
+
+void refit_emitter_tables(const EmTables &t, const float *vpos, const uint32_t *tri_vidx, const float *tables,
+                          uint32_t *state, hipStream_t st) {
+  if (t.n_slots == 0) return;
+  hipLaunchKernelGGL(k_em_areas, t.n_blocks, kEmBlock, 0, st, t, vpos, tri_vidx, tables);
+  hipLaunchKernelGGL(k_em_reduce, t.n_slots, kEmBlock, 0, st, t);
+  hipLaunchKernelGGL(k_em_scan, t.n_blocks, kEmBlock, 0, st, t);
+  hipLaunchKernelGGL(k_em_scan_ordered, t.n_slots, 64, 0, st, t);
+  hipLaunchKernelGGL(k_em_finish, blocks(t.n_slots), kBlock, 0, st, t, state);
+}
+
+void refit_emitter_commit(const EmTables &t, float *tables, mtx_emitter *emitters, hipStream_t st) {
+  if (t.n_slots == 0) return;
+  hipLaunchKernelGGL(k_em_commit, t.n_blocks, kEmBlock, 0, st, t, tables, emitters);
 }
 
 void refit_triangles(const float *vpos, const float *vnormal, const uint32_t *tri_vidx, uint32_t n_tris, float *tri,

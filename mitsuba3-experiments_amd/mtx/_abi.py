@@ -354,4 +354,5 @@ EXPORTS = [
     "mtx_bvh_refit_occlusion",
     "mtx_scene_update_vertices",
     "mtx_scene_read",
+    "mtx_tri_area_f32",
 ]

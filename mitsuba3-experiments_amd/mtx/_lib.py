@@ -93,6 +93,7 @@ def lib() -> C.CDLL:
         "mtx_bvh_refit_occlusion": ([vp, vp, u32, vp, u32, vp], C.c_int),
         "mtx_scene_update_vertices": ([vp, vp, vp, u32, C.c_int], C.c_int),
         "mtx_scene_read": ([vp, C.c_int, vp, u64], C.c_int),
+        "mtx_tri_area_f32": ([vp, u64, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -141,9 +142,11 @@ class Context:
         ``mi.traverse(scene)``. `vpos` / `vnormal`: (n_verts, 3) float32
         numpy arrays, or torch CUDA tensors on this context's device (a
         simulation that lives on the GPU: nothing passes through the host; the
-        tensors' producer is synchronised first). Topology stays; emitter
-        shapes must not move; MtxError with the reason otherwise, and the
-        device scene is then unchanged.
+        tensors' producer is synchronised first). Topology stays; mesh
+        emitters move with their vertices (their tables and records are
+        rebuilt on the device); rectangle emitter shapes must not move;
+        MtxError with the reason otherwise, and the device scene is then
+        unchanged.
 
         The host ``Scene`` this context was bound to is stale afterwards: the
         context forgets it, so the next scene rendered through it is uploaded
@@ -179,16 +182,19 @@ class Context:
     def scene_read(self, which: str):
         """The device copy of one scene array (mtx_scene_read; tests and
         debugging): 'nodes', 'occ_nodes', 'tri', 'occ_tri', 'shade_rec',
-        'vpos', 'vnormal' or 'env_sphere'. `n_*` come from the bound scene."""
+        'vpos', 'vnormal', 'env_sphere', 'tables' or 'emitters' (the records
+        as uint32 words, 16 each). `n_*` come from the bound scene."""
         import numpy as np
-        names = ["nodes", "occ_nodes", "tri", "occ_tri", "shade_rec", "vpos", "vnormal", "env_sphere"]
+        names = ["nodes", "occ_nodes", "tri", "occ_tri", "shade_rec", "vpos", "vnormal", "env_sphere", "tables",
+                 "emitters"]
         s = getattr(self, "_read_counts", None)
         if s is None:
             raise MtxError("scene_read: no scene was bound to this context")
         size = {"nodes": (16 * s["n_nodes"], np.int32), "occ_nodes": (20 * s["n_occ_nodes"], np.int32),
                 "tri": (9 * s["n_tris"], np.float32), "occ_tri": (9 * s["n_tris"], np.float32),
                 "shade_rec": (32 * s["n_tris"], np.float32), "vpos": (3 * s["n_verts"], np.float32),
-                "vnormal": (3 * s["n_verts"], np.float32), "env_sphere": (4, np.float32)}[which]
+                "vnormal": (3 * s["n_verts"], np.float32), "env_sphere": (4, np.float32),
+                "tables": (s["n_tables"], np.float32), "emitters": (16 * s["n_emitters"], np.uint32)}[which]
         out = np.zeros(size[0], size[1])
         check(lib().mtx_scene_read(self._h, names.index(which), out.ctypes.data, out.nbytes), "mtx_scene_read")
         return out

@@ -578,8 +578,9 @@ def _bind_scene(ctx, scene) -> None:
     camera (mtx_set_camera). A scene made from the bound one by
     Scene.with_vertices (same geometry-base token and film size, other node
     arrays) is not uploaded either: its vertices go through
-    mtx_scene_update_vertices, which refits both trees on the device
-    (MTX_REFIT_UPLOAD=1 forces the full upload, for A/B runs)."""
+    mtx_scene_update_vertices, which refits both trees and rebuilds the mesh
+    emitters' tables and records on the device, as with_vertices did on the
+    host (MTX_REFIT_UPLOAD=1 forces the full upload, for A/B runs)."""
     key = (id(scene.nodes), scene.width, scene.height)
     if getattr(ctx, "_scene_key", None) == key:
         if getattr(ctx, "_camera", None) != bytes(scene.camera):
@@ -590,9 +591,12 @@ def _bind_scene(ctx, scene) -> None:
     token = getattr(scene, "_geom_token", None)
     bound, prev = getattr(ctx, "_scene_key", None), ctx.scene
     # everything a vertex update does not carry must be the bound scene's own
-    shared = ("tri_vidx", "tri_shape", "vuv", "shapes", "materials", "emitters", "textures", "texels", "tables")
+    # (emitters and tables: the bound scene's own, or rebuilt from them by with_vertices, which the device update
+    # rebuilds alike -- compared through their root, so a copy given other tables is uploaded in full)
+    shared = ("tri_vidx", "tri_shape", "vuv", "shapes", "materials", "textures", "texels")
+    root_p, root_s = prev._emitter_root() if prev is not None else (None, None), scene._emitter_root()
     if (token is not None and getattr(ctx, "_geom_token", None) is token and bound is not None and prev is not None
-            and bound[1:] == key[1:] and os.environ.get("MTX_REFIT_UPLOAD", "0") != "1"
+            and root_p[0] is root_s[0] and root_p[1] is root_s[1] and bound[1:] == key[1:] and os.environ.get("MTX_REFIT_UPLOAD", "0") != "1"
             and all(getattr(prev, a, None) is getattr(scene, a, None) for a in shared)
             and getattr(prev, "env_radiance", None) == getattr(scene, "env_radiance", None)):
         ctx.update_vertices(scene.vpos, scene.vnormal)  # forgets the bound scene
@@ -601,7 +605,8 @@ def _bind_scene(ctx, scene) -> None:
         d = scene.desc()
         check(lib().mtx_scene_upload(ctx.handle, C.byref(d)), "mtx_scene_upload")
         ctx._read_counts = {"n_nodes": int(scene.n_nodes), "n_occ_nodes": int(scene.n_occ_nodes),
-                            "n_tris": int(scene.n_tris), "n_verts": int(d.n_verts)}
+                            "n_tris": int(scene.n_tris), "n_verts": int(d.n_verts),
+                            "n_tables": int(d.n_tables), "n_emitters": int(d.n_emitters)}
     ctx._geom_token = token
     ctx._scene_key = key
     ctx._camera = bytes(scene.camera)

@@ -330,16 +330,10 @@ class Scene:
         blocks, off = [self.tables[: self.n_tables]], self.n_tables
         for em in mesh_emitters:
             prims = np.flatnonzero(tri_em == em).astype(np.uint32)
-            p0, p1, p2 = (v[vid[prims, k]] for k in range(3))
-            pmf = _tri_area_f32(p0, p1, p2)
-            cdf = np.cumsum(pmf.astype(np.float64)).astype(np.float32)
-            nz = np.flatnonzero(pmf > 0)
-            if len(nz) == 0 or not np.isfinite(cdf[-1]):
-                raise MtxError(f"mesh emitter {em}: its {len(prims)} triangles have no finite positive area")
-            total = np.float32(cdf[-1])
+            pmf, cdf, lo, hi, total, norm = _mesh_distribution(v, vid, prims, em)
             e = self.emitters[em]
-            e.set_mesh(off, len(prims), nz[0], nz[-1], total, np.float32(1.0) / total)
-            e.inv_area = np.float32(1.0) / total
+            e.set_mesh(off, len(prims), lo, hi, total, norm)
+            e.inv_area = norm
             blocks += [pmf, cdf, prims.view(np.float32)]
             off += 3 * len(prims)
         self.tables = np.ascontiguousarray(np.concatenate(blocks).astype(np.float32, copy=False))
@@ -425,7 +419,7 @@ class Scene:
         s.meta = dict(self.meta, width=int(c2.width), height=int(c2.height))
         return s
 
-    def with_vertices(self, vpos, vnormal=None) -> "Scene":
+    def with_vertices(self, vpos, vnormal=None, move_emitters: bool = False) -> "Scene":
         """The scene with moved vertices: assigning ``vertex_positions`` and
         calling ``params.update()`` on ``mi.traverse(scene)``. Topology, leaf
         order, materials and everything else are shared with this scene; the
@@ -433,10 +427,24 @@ class Scene:
         ``tri_geom``, ``occ_tri_geom`` and both trees' nodes, refit on the
         host (mtx_bvh_refit, mtx_bvh_refit_occlusion) -- no rebuild. A context
         bound to this scene takes the new one through the device refit
-        (integrators._bind_scene). Raises MtxError for a wrong vertex count, a
-        non-finite or huge coordinate, or a moved vertex of an emitter shape
-        (rectangle emitters are analytic and a mesh emitter's triangle tables
-        are built at load time; neither can be animated)."""
+        (integrators._bind_scene).
+
+        With ``move_emitters=True`` mesh emitters move with their vertices
+        (the default keeps refusing a moved mesh-light vertex, as before mesh
+        lights could move, so a caller that relied on the refusal still gets
+        it): for every mesh emitter with a
+        moved vertex, pmf, cdf, valid range, sum, normalization and inv_area
+        are rebuilt by the loader's own code (_mesh_distribution) at the new
+        positions, in this scene's entry order; the new scene then has its own
+        ``tables`` and ``emitters`` (this scene's are not written). Unchanged
+        vertices give back the loader's bits.
+
+        Raises MtxError for a wrong vertex count, a non-finite or huge
+        coordinate, a moved vertex of a mesh emitter shape without
+        ``move_emitters``, a mesh emitter left without a finite positive area, or
+        a moved vertex of a rectangle emitter shape (a rectangle emitter is an
+        analytic record derived from to_world, not from its vertices, and
+        cannot be animated)."""
         import copy
 
         from ._lib import MtxError, check, lib
@@ -452,15 +460,35 @@ class Scene:
                 raise MtxError(f"with_vertices: {len(vnormal)} normals for {len(vpos)} vertices")
         vpos = vpos.reshape(self.vpos.shape)
         vnormal = vnormal.reshape(self.vnormal.shape)
-        em_shape = np.array([sh.emitter >= 0 for sh in self.shapes], bool)
-        em_verts = np.unique(self.tri_vidx.reshape(-1, 3)[em_shape[self.tri_shape]])
+        shape_em = np.array([sh.emitter for sh in self.shapes], np.int64)
+        is_mesh = np.array([e.is_mesh for e in self.emitters], bool)
+        tri_em = shape_em[self.tri_shape]
+        vid = self.tri_vidx.reshape(-1, 3)
         old3, new3 = self.vpos.reshape(-1, 3), vpos.reshape(-1, 3)
-        if not np.array_equal(old3[em_verts].view(np.uint32), new3[em_verts].view(np.uint32)):
-            raise MtxError("with_vertices: a vertex of an emitter shape would move (a moved emitter vertex: a "
-                           "rectangle emitter is held analytically and a mesh emitter's triangle distribution is "
-                           "built at load time, so a moved mesh light would need its tables rebuilt; neither can be "
-                           "animated)")
+        moved = (old3.view(np.uint32) != new3.view(np.uint32)).any(1)
+        tri_moved = moved[vid].any(1) & (tri_em >= 0)
+        if len(is_mesh) and (tri_moved & ~is_mesh[np.maximum(tri_em, 0)]).any():
+            raise MtxError("with_vertices: a vertex of a rectangle emitter shape would move (a rectangle emitter is an "
+                           "analytic record derived from to_world, not from its vertices, and cannot be animated; "
+                           "mesh emitters can)")
+        rebuilt = np.unique(tri_em[tri_moved])
+        if len(rebuilt) and not move_emitters:
+            raise MtxError("with_vertices: a vertex of a mesh emitter shape would move (a moved emitter vertex: the "
+                           "mesh light needs its tables rebuilt; pass move_emitters=True to move it and rebuild them)")
         s = copy.copy(self)
+        if len(rebuilt):
+            root = self._emitter_root()
+            s.emitters = type(self.emitters).from_buffer_copy(bytes(self.emitters))
+            s.tables = np.array(self.tables, np.float32)
+            for em in rebuilt:
+                m = s.emitters[em].mesh
+                n, off = m["count"], m["offset"]
+                prims = s.tables[off + 2 * n: off + 3 * n].view(np.uint32)
+                pmf, cdf, lo, hi, total, norm = _mesh_distribution(new3, vid, prims, int(em))
+                s.tables[off: off + n], s.tables[off + n: off + 2 * n] = pmf, cdf
+                s.emitters[em].set_mesh(off, n, lo, hi, total, norm)
+                s.emitters[em].inv_area = norm
+            s._emitter_root_ = (root[0], root[1], s.emitters, s.tables)
         s.vpos, s.vnormal = vpos.copy(), vnormal.copy()
         s.nodes, s.occ_nodes = self.nodes.copy(), self.occ_nodes.copy()
         s.tri_geom, s.occ_tri_geom = np.zeros_like(self.tri_geom), np.zeros_like(self.occ_tri_geom)
@@ -472,6 +500,17 @@ class Scene:
                                             s.occ_nodes.ctypes.data, s.n_occ_nodes, s.occ_tri_geom.ctypes.data),
               "mtx_bvh_refit_occlusion")
         return s
+
+    def _emitter_root(self) -> tuple:
+        """(emitters, tables) this scene's were derived from by vertex updates
+        alone (with_vertices), else its own: scenes with one root and one
+        geometry base differ in nothing a device vertex update does not
+        rebuild. A copy whose emitters or tables were replaced is its own
+        root."""
+        r = getattr(self, "_emitter_root_", None)
+        if r is not None and r[2] is self.emitters and r[3] is self.tables:
+            return r[0], r[1]
+        return self.emitters, self.tables
 
     def env_sphere(self) -> np.ndarray:
         """(centre.xyz, radius) of the constant environment's bounding sphere
@@ -581,6 +620,26 @@ class Sensor:
 
     def film_size(self) -> tuple:
         return int(self.camera.width), int(self.camera.height)
+
+
+def _mesh_distribution(v, vid, prims, em):
+    """One mesh emitter's DiscreteDistribution over the triangles `prims` (in
+    this order) of vertices `v` (n, 3) and indices `vid` (n_tris, 3): pmf the
+    fp32 areas, cdf their inclusive prefix accumulated sequentially in double
+    and stored as float, the first / last entry with pmf > 0, sum = cdf[-1]
+    and normalization = 1 / sum in fp32. Shared by the loader and
+    Scene.with_vertices; MtxError when no finite positive total is left."""
+    from ._lib import MtxError
+    p0, p1, p2 = (v[vid[prims, k]] for k in range(3))
+    with np.errstate(all="ignore"):  # an overflowing area is refused below
+        pmf = _tri_area_f32(p0, p1, p2)
+        cdf = np.cumsum(pmf.astype(np.float64)).astype(np.float32)
+        nz = np.flatnonzero(pmf > 0)
+        total = np.float32(cdf[-1])
+        norm = np.float32(1.0) / total
+    if len(nz) == 0 or not np.isfinite(pmf).all() or not (np.isfinite(total) and total > 0 and np.isfinite(norm)):
+        raise MtxError(f"mesh emitter {em}: its {len(prims)} triangles have no finite positive area")
+    return pmf, cdf, int(nz[0]), int(nz[-1]), total, norm
 
 
 def _tri_area_f32(p0, p1, p2):
