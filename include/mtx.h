@@ -520,6 +520,131 @@ int mtx_trace(mtx_ctx *ctx, uint64_t n, const float *rays, int any_hit, uint32_t
 int mtx_trace_dev(mtx_ctx *ctx, uint64_t n, const float *rays, int any_hit, uint32_t *hits,
                   uint32_t *visits);
 
+/* --------------------------- building blocks ---------------------- */
+/* The calls the reference's integrators are composed of (path-mis.py:69-121,
+ * simple.py:57-114), one wavefront-wide kernel each, for estimators written
+ * in Python on device tensors (mtx.blocks; INTEGRATION.md "Writing an
+ * integrator on the blocks"). Every buffer is device memory of the context's
+ * device in the facade's Dr.Jit layout: a quantity of C components over n
+ * items is one contiguous (C, n) array, component c of item i at [c * n + i];
+ * masks are n bytes (0 = off). A host pointer is refused (MTX_E_ARG). Work
+ * runs on the context's stream and is complete on return; the caller orders
+ * its own producers before the call. There are no host twins. n = 0 returns
+ * at once; n < 2^31.
+ *   Indices that arrive in caller tensors (material, emitter, prim) are
+ * compared against the scene's counts on the device before any load that
+ * depends on them: one out of range is treated as invalid (null BSDF, no
+ * emitter, a miss), the outputs are complete, and the call returns MTX_E_ARG
+ * with the number of such lanes in the message.
+ *   `active` may be NULL (all lanes). A masked-off lane writes the zero /
+ * invalid values and is never traced. */
+
+/* Surface interaction planes (SurfaceInteraction3f as the reference's loops
+ * use it). The shading frame is not stored: every consumer rebuilds it from
+ * sh_n (mtx_core/warp.h frame_from_normal, a function of the normal alone). */
+typedef struct mtx_si_planes {
+  float *p, *n, *sh_n;   /* (3, n) position, geometric and shading normal */
+  float *uv;             /* (2, n) */
+  float *wi;             /* (3, n) incident direction, local frame */
+  float *t;              /* (n) ray distance, inf for an invalid interaction */
+  uint32_t *prim;        /* (n) leaf-order triangle, 0xffffffff = none */
+  int32_t *material;     /* (n) -1 for an invalid interaction */
+  int32_t *emitter;      /* (n) -1 = none; a miss under an environment: n_emitters */
+  float *bary;           /* (2, n) barycentrics of the hit record (u, v); may be NULL */
+} mtx_si_planes;
+
+/* DirectionSample3f planes of emitter sampling. */
+typedef struct mtx_ds_planes {
+  float *p, *n, *d;      /* (3, n) */
+  float *dist, *pdf;     /* (n) */
+  int32_t *emitter;      /* (n) */
+} mtx_ds_planes;
+
+/* Outputs of bsdf.eval_pdf_sample. */
+typedef struct mtx_bsdf_planes {
+  float *value;          /* (3, n) eval at wo */
+  float *pdf;            /* (n) pdf at wo */
+  float *s_wo;           /* (3, n) sampled direction, local */
+  float *s_pdf, *s_eta;  /* (n) */
+  uint32_t *s_type;      /* (n) sampled component's BSDFFlags */
+  float *weight;         /* (3, n) sample weight */
+} mtx_bsdf_planes;
+
+/* sampler.seed (IndependentSampler over the given lane ids, restirgi.py:203):
+ * state[i] = the PCG32 of (seed, lanes[i]) advanced by skip draws, two 64-bit
+ * words per lane (state, sequence id). Needs no scene. */
+int mtx_blocks_sampler_seed_dev(mtx_ctx *ctx, uint64_t n, uint32_t seed, const uint32_t *lanes, uint32_t skip,
+                                uint64_t *state);
+/* sampler.next_1d (dims = 1: out is (n)) / next_2d (dims = 2: out is (2, n))
+ * (path-mis.py:97,104-105,147). Advances the state of every lane in place. */
+int mtx_blocks_sampler_next_dev(mtx_ctx *ctx, uint64_t n, uint64_t *state, int dims, float *out);
+/* scene.ray_intersect (path-mis.py:69-71): closest-hit traversal of the rays
+ * o, d (3, n) with maxt (n; NULL = the largest float) and the surface
+ * interaction of each hit, in one launch. The direction contract of
+ * mtx_trace applies: d need not be normalised, its largest component
+ * magnitude must lie in [2^-40, 2^60], (0, 0, 0) misses, non-finite rays are
+ * outside the contract. A miss is the invalid interaction with emitter =
+ * n_emitters under an environment, else -1; a masked-off lane is invalid
+ * with emitter = -1 and wi = -d. */
+int mtx_blocks_ray_intersect_dev(mtx_ctx *ctx, uint64_t n, const float *o, const float *d, const float *maxt,
+                                 const uint8_t *active, const mtx_si_planes *si);
+/* scene.ray_test (restirgi.py:320): any-hit traversal, out[i] = 1 if
+ * occluded within maxt (required). mtx_trace's direction contract applies.
+ * Masked-off lanes give 0. */
+int mtx_blocks_ray_test_dev(mtx_ctx *ctx, uint64_t n, const float *o, const float *d, const float *maxt,
+                            const uint8_t *active, uint8_t *out);
+/* The interaction half of scene.ray_intersect (path-mis.py:69-71) for hit
+ * records the caller holds (mtx_trace_dev's t, prim, u, v; ray direction d): what
+ * Mesh::compute_surface_interaction gives. prim = 0xffffffff is a miss. */
+int mtx_blocks_interact_dev(mtx_ctx *ctx, uint64_t n, const float *d, const float *t, const uint32_t *prim,
+                            const float *u, const float *v, const uint8_t *active, const mtx_si_planes *si);
+/* si.spawn_ray(d) (to = 0, path-mis.py:121) / si.spawn_ray_to(target)
+ * (to = 1) from p, n (3, n) and x = the direction or the target: o, d (3, n)
+ * and maxt (n). Needs no scene. */
+int mtx_blocks_spawn_dev(mtx_ctx *ctx, uint64_t n, const float *p, const float *nrm, const float *x, int to,
+                         float *o, float *d, float *maxt);
+/* scene.sample_emitter_direction(si, u, test_visibility) (path-mis.py:94-98)
+ * from the reference point p, its geometric normal nrm (3, n; read only with
+ * test_visibility) and u (2, n): ds and the weight (3, n). test_visibility
+ * != 0 traces spawn_ray_to(p, nrm, ds.p) through the any-hit tree in the
+ * same launch and zeroes the weight of an occluded sample. A scene without
+ * emitters gives zeros. */
+int mtx_blocks_sample_emitter_dev(mtx_ctx *ctx, uint64_t n, const float *p, const float *nrm, const float *u,
+                                  const uint8_t *active, int test_visibility, const mtx_ds_planes *ds,
+                                  float *weight);
+/* scene.pdf_emitter_direction (path-mis.py:78) and emitter.eval
+ * (path-mis.py:83) for the emitter index of each lane (-1 = none): pdf (n)
+ * from the direction d (3, n) towards the emitter, its distance dist (n) and
+ * the emitter-side normal nrm (3, n); le (3, n) from the local incident
+ * direction wi (3, n). Either output group may be NULL with its inputs. */
+int mtx_blocks_emitter_dev(mtx_ctx *ctx, uint64_t n, const int32_t *emitter, const float *d, const float *dist,
+                           const float *nrm, const float *wi, const uint8_t *active, float *pdf, float *le);
+/* bsdf.eval_pdf_sample (path-mis.py:104-109) of the material index of each
+ * lane (< 0: the null BSDF, all zeros) at uv (2, n), wi and wo (3, n, local),
+ * u1 (n), u2 (2, n); flags (n, may be NULL): bsdf.flags() of the lane's
+ * material (path.py:245), 0 for the null BSDF. out = NULL with flags given
+ * evaluates the flags alone (uv .. u2 are then not read). */
+int mtx_blocks_bsdf_dev(mtx_ctx *ctx, uint64_t n, const int32_t *material, const float *uv, const float *wi,
+                        const float *wo, const float *u1, const float *u2, const uint8_t *active,
+                        const mtx_bsdf_planes *out, uint32_t *flags);
+/* Exact elementwise arithmetic in the oracle's rounding (mtx_core/common.h,
+ * warp.h, interaction.h): dr.fma and the operations whose rounding a tensor
+ * library does not pin. n items; a, b, c as the op needs (else NULL):
+ *   FMA  out = fmaf(a, b, c)          DIV  out = a / b
+ *   RCP  out = 1 / a                  SQRT out = sqrtf(a)        (1 component)
+ *   DOT3 out (n) = dot(a, b)          NORM3 out (n) = norm(a)
+ *   NORMALIZE3 out (3, n)             (a, b of 3 components)
+ *   TO_LOCAL / TO_WORLD out (3, n) = b in / out of the frame of the normal a
+ *   MIS_A / MIS_B out (n) = the power heuristic of path.py:10-18 /
+ *   path-mis.py:9-15 for the pdfs a, b. */
+enum {
+  MTX_MATH_FMA = 0, MTX_MATH_DIV = 1, MTX_MATH_RCP = 2, MTX_MATH_SQRT = 3, MTX_MATH_DOT3 = 4,
+  MTX_MATH_NORM3 = 5, MTX_MATH_NORMALIZE3 = 6, MTX_MATH_TO_LOCAL = 7, MTX_MATH_TO_WORLD = 8,
+  MTX_MATH_MIS_A = 9, MTX_MATH_MIS_B = 10
+};
+int mtx_blocks_math_dev(mtx_ctx *ctx, int op, uint64_t n, const float *a, const float *b, const float *c,
+                        float *out);
+
 /* --------------------------- film filters ------------------------- */
 /* Host-only: border (pixels on every side of the raw film) and radius of a
  * reconstruction filter; either output may be NULL. Unknown id: MTX_E_ARG. */

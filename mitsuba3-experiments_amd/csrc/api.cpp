@@ -22,6 +22,7 @@
 #include "mtx.h"
 #include "mtx_core/film.h"
 #include "mtx_core/interaction.h"
+#include "blocks.h"
 #include "prims.h"
 #include "refit.h"
 #include "wavefront.h"
@@ -167,6 +168,7 @@ struct mtx_ctx {
   mtx::NeradTables nr{};
   bool has_nerad = false;
   uint32_t scene_n_shapes = 0;
+  uint32_t scene_n_materials = 0;  // bound of the material indices the building blocks take (blocks.hip)
   DevBuf nr_lhs, nr_qp, nr_qd, nr_Lrhs, nr_lanes;
   DevBuf nodes, tri, occ_nodes, occ_tri, tri_vidx, tri_shape, vpos, vnormal, vuv, shapes, materials, emitters, textures, texels, tables;
   mtxd::DevScene scene{};
@@ -769,6 +771,7 @@ int mtx_scene_upload(mtx_ctx *c, const mtx_scene_desc *d) {
   s.tables = (const float *)c->tables.p;
   s.n_tris = d->n_tris;
   s.n_emitters = d->n_emitters;
+  c->scene_n_materials = d->n_materials;
   s.camera = d->camera;
   s.has_env = d->has_env ? 1u : 0u;
   for (int k = 0; k < 3; ++k) s.env_radiance[k] = d->env_radiance[k];
@@ -2931,6 +2934,211 @@ int mtx_nerad_step(mtx_ctx *c, const mtx_nerad_args *a, mtx_train_stats *stats) 
   st.ms_total = pt.ms(0, 3);
   if (stats) *stats = st;
   return MTX_OK;
+}
+
+}  // extern "C"
+
+// ----------------------------- building blocks -----------------------------
+// One entry per kernel group of blocks.hip. Order: argument checks,
+// need_device on every pointer before anything touches it, the launch on the
+// context's stream, the stream drained, then the device counter of lanes
+// whose index lay outside the scene's tables (the kernels treat those as
+// invalid and never index with them).
+
+static int blk_begin(mtx_ctx *c, const char *fn, uint64_t n, bool scene, std::initializer_list<const void *> need) {
+  if (!c) {
+    mtx_set_error("%s: null context", fn);
+    return MTX_E_ARG;
+  }
+  if (scene && !c->has_scene) {
+    mtx_set_error("no scene uploaded");
+    return MTX_E_NOSCENE;
+  }
+  if (n >= (1ull << 31)) {
+    mtx_set_error("%s: n >= 2^31", fn);
+    return MTX_E_ARG;
+  }
+  if (n == 0) return MTX_OK;
+  for (const void *p : need)
+    if (!p) {
+      mtx_set_error("%s: null argument", fn);
+      return MTX_E_ARG;
+    }
+  HIP_TRY(hipSetDevice(c->device));
+  return MTX_OK;
+}
+static int blk_bad_reset(mtx_ctx *c) {
+  if (int rc = dalloc(c->s6, 64)) return rc;
+  HIP_TRY(hipMemsetAsync(c->s6.p, 0, 4, c->stream));
+  return MTX_OK;
+}
+static int blk_end(mtx_ctx *c, const char *fn, const char *what) {
+  HIP_TRY(hipGetLastError());
+  uint32_t bad = 0;
+  if (what) HIP_TRY(hipMemcpyAsync(&bad, c->s6.p, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (bad) {
+    mtx_set_error("%s: %u lanes with %s (handled as invalid)", fn, bad, what);
+    return MTX_E_ARG;
+  }
+  return MTX_OK;
+}
+static int si_need_device(mtx_ctx *c, const char *fn, const mtx_si_planes *si) {
+  if (!si->p || !si->n || !si->sh_n || !si->uv || !si->wi || !si->t || !si->prim || !si->material || !si->emitter) {
+    mtx_set_error("%s: null interaction plane", fn);
+    return MTX_E_ARG;
+  }
+  return need_device(c, fn, {si->p, si->n, si->sh_n, si->uv, si->wi, si->t, si->prim, si->material, si->emitter,
+                             si->bary});
+}
+
+extern "C" {
+
+int mtx_blocks_sampler_seed_dev(mtx_ctx *c, uint64_t n, uint32_t seed, const uint32_t *lanes, uint32_t skip,
+                                uint64_t *state) {
+  const char *fn = "mtx_blocks_sampler_seed_dev";
+  int rc = blk_begin(c, fn, n, false, {lanes, state});
+  if (rc || n == 0) return rc;
+  if ((rc = need_device(c, fn, {lanes, state}))) return rc;
+  mtxd::launch_blk_seed((uint32_t)n, seed, lanes, skip, state, c->stream);
+  return blk_end(c, fn, nullptr);
+}
+
+int mtx_blocks_sampler_next_dev(mtx_ctx *c, uint64_t n, uint64_t *state, int dims, float *out) {
+  const char *fn = "mtx_blocks_sampler_next_dev";
+  int rc = blk_begin(c, fn, n, false, {state, out});
+  if (rc) return rc;
+  if (dims != 1 && dims != 2) {
+    mtx_set_error("%s: dims %d (1 or 2)", fn, dims);
+    return MTX_E_ARG;
+  }
+  if (n == 0) return MTX_OK;
+  if ((rc = need_device(c, fn, {state, out}))) return rc;
+  mtxd::launch_blk_next((uint32_t)n, state, dims, out, c->stream);
+  return blk_end(c, fn, nullptr);
+}
+
+int mtx_blocks_ray_intersect_dev(mtx_ctx *c, uint64_t n, const float *o, const float *d, const float *maxt,
+                                 const uint8_t *active, const mtx_si_planes *si) {
+  const char *fn = "mtx_blocks_ray_intersect_dev";
+  int rc = blk_begin(c, fn, n, true, {o, d, si});
+  if (rc || n == 0) return rc;
+  if ((rc = need_device(c, fn, {o, d, maxt, active})) || (rc = si_need_device(c, fn, si))) return rc;
+  // the traversal yields its own prim: nothing to range-check, no counter
+  mtxd::launch_blk_interact(c->scene, (uint32_t)n, 1, o, d, maxt, nullptr, nullptr, nullptr, nullptr, active, *si,
+                            nullptr, c->stream);
+  return blk_end(c, fn, nullptr);
+}
+
+int mtx_blocks_ray_test_dev(mtx_ctx *c, uint64_t n, const float *o, const float *d, const float *maxt,
+                            const uint8_t *active, uint8_t *out) {
+  const char *fn = "mtx_blocks_ray_test_dev";
+  int rc = blk_begin(c, fn, n, true, {o, d, maxt, out});
+  if (rc || n == 0) return rc;
+  if ((rc = need_device(c, fn, {o, d, maxt, active, out}))) return rc;
+  mtxd::launch_blk_ray_test(c->scene, (uint32_t)n, o, d, maxt, active, out, c->stream);
+  return blk_end(c, fn, nullptr);
+}
+
+int mtx_blocks_interact_dev(mtx_ctx *c, uint64_t n, const float *d, const float *t, const uint32_t *prim,
+                            const float *u, const float *v, const uint8_t *active, const mtx_si_planes *si) {
+  const char *fn = "mtx_blocks_interact_dev";
+  int rc = blk_begin(c, fn, n, true, {d, t, prim, u, v, si});
+  if (rc || n == 0) return rc;
+  if ((rc = need_device(c, fn, {d, t, prim, u, v, active})) || (rc = si_need_device(c, fn, si)) ||
+      (rc = blk_bad_reset(c)))
+    return rc;
+  mtxd::launch_blk_interact(c->scene, (uint32_t)n, 0, nullptr, d, nullptr, t, prim, u, v, active, *si,
+                            (uint32_t *)c->s6.p, c->stream);
+  return blk_end(c, fn, "a prim that is neither a triangle of the scene nor 0xffffffff");
+}
+
+int mtx_blocks_spawn_dev(mtx_ctx *c, uint64_t n, const float *p, const float *nrm, const float *x, int to, float *o,
+                         float *d, float *maxt) {
+  const char *fn = "mtx_blocks_spawn_dev";
+  int rc = blk_begin(c, fn, n, false, {p, nrm, x, o, d, maxt});
+  if (rc || n == 0) return rc;
+  if ((rc = need_device(c, fn, {p, nrm, x, o, d, maxt}))) return rc;
+  mtxd::launch_blk_spawn((uint32_t)n, p, nrm, x, to != 0, o, d, maxt, c->stream);
+  return blk_end(c, fn, nullptr);
+}
+
+int mtx_blocks_sample_emitter_dev(mtx_ctx *c, uint64_t n, const float *p, const float *nrm, const float *u,
+                                  const uint8_t *active, int test_visibility, const mtx_ds_planes *ds,
+                                  float *weight) {
+  const char *fn = "mtx_blocks_sample_emitter_dev";
+  int rc = blk_begin(c, fn, n, true, {p, u, ds, weight});
+  if (rc || n == 0) return rc;
+  if (!ds->p || !ds->n || !ds->d || !ds->dist || !ds->pdf || !ds->emitter || (test_visibility && !nrm)) {
+    mtx_set_error("%s: null argument", fn);
+    return MTX_E_ARG;
+  }
+  if ((rc = need_device(c, fn, {p, nrm, u, active, ds->p, ds->n, ds->d, ds->dist, ds->pdf, ds->emitter, weight})))
+    return rc;
+  mtxd::launch_blk_sample_emitter(c->scene, (uint32_t)n, p, nrm, u, active, test_visibility != 0, *ds, weight,
+                                  c->stream);
+  return blk_end(c, fn, nullptr);
+}
+
+int mtx_blocks_emitter_dev(mtx_ctx *c, uint64_t n, const int32_t *emitter, const float *d, const float *dist,
+                           const float *nrm, const float *wi, const uint8_t *active, float *pdf, float *le) {
+  const char *fn = "mtx_blocks_emitter_dev";
+  int rc = blk_begin(c, fn, n, true, {emitter});
+  if (rc || n == 0) return rc;
+  if ((!pdf && !le) || (pdf && (!d || !dist || !nrm)) || (le && !wi)) {
+    mtx_set_error("%s: null argument", fn);
+    return MTX_E_ARG;
+  }
+  if ((rc = need_device(c, fn, {emitter, d, dist, nrm, wi, active, pdf, le})) || (rc = blk_bad_reset(c))) return rc;
+  mtxd::launch_blk_emitter(c->scene, (uint32_t)n, emitter, d, dist, nrm, wi, active, pdf, le, (uint32_t *)c->s6.p,
+                           c->stream);
+  return blk_end(c, fn, "an emitter index past the scene's emitters");
+}
+
+int mtx_blocks_bsdf_dev(mtx_ctx *c, uint64_t n, const int32_t *material, const float *uv, const float *wi,
+                        const float *wo, const float *u1, const float *u2, const uint8_t *active,
+                        const mtx_bsdf_planes *out, uint32_t *flags) {
+  const char *fn = "mtx_blocks_bsdf_dev";
+  int rc = blk_begin(c, fn, n, true, {material});
+  if (rc || n == 0) return rc;
+  mtx_bsdf_planes o{};
+  if (out) {
+    o = *out;
+    if (!uv || !wi || !wo || !u1 || !u2 || !o.value || !o.pdf || !o.s_wo || !o.s_pdf || !o.s_eta || !o.s_type ||
+        !o.weight) {
+      mtx_set_error("%s: null argument", fn);
+      return MTX_E_ARG;
+    }
+  } else if (!flags) {
+    mtx_set_error("%s: neither outputs nor flags", fn);
+    return MTX_E_ARG;
+  }
+  if ((rc = need_device(c, fn, {material, uv, wi, wo, u1, u2, active, o.value, o.pdf, o.s_wo, o.s_pdf, o.s_eta,
+                                o.s_type, o.weight, flags})) ||
+      (rc = blk_bad_reset(c)))
+    return rc;
+  mtxd::launch_blk_bsdf(c->scene, c->scene_n_materials, (uint32_t)n, material, uv, wi, wo, u1, u2, active, o, flags,
+                        (uint32_t *)c->s6.p, c->stream);
+  return blk_end(c, fn, "a material index past the scene's materials");
+}
+
+int mtx_blocks_math_dev(mtx_ctx *c, int op, uint64_t n, const float *a, const float *b, const float *cc, float *out) {
+  const char *fn = "mtx_blocks_math_dev";
+  int rc = blk_begin(c, fn, n, false, {a, out});
+  if (rc) return rc;
+  const bool need_b = op != MTX_MATH_RCP && op != MTX_MATH_SQRT && op != MTX_MATH_NORM3 && op != MTX_MATH_NORMALIZE3;
+  if (op < MTX_MATH_FMA || op > MTX_MATH_MIS_B) {
+    mtx_set_error("%s: unknown op %d", fn, op);
+    return MTX_E_ARG;
+  }
+  if (n == 0) return MTX_OK;
+  if ((need_b && !b) || (op == MTX_MATH_FMA && !cc)) {
+    mtx_set_error("%s: null argument", fn);
+    return MTX_E_ARG;
+  }
+  if ((rc = need_device(c, fn, {a, b, cc, out}))) return rc;
+  mtxd::launch_blk_math(op, (uint32_t)n, a, b, cc, out, c->stream);
+  return blk_end(c, fn, nullptr);
 }
 
 }  // extern "C"

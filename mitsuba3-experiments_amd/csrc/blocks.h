@@ -1,0 +1,39 @@
+// blocks.h — launch wrappers of the device-tensor building blocks
+// (blocks.hip): wavefront-wide kernels over the per-lane functions of
+// mtx_core, on SoA planes ((C, N) contiguous, plane c of item i at [c * N + i]).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mtx.h"
+#include "wavefront.h"
+
+namespace mtxd {
+
+// `n` lanes; pointers are device memory, laid out as mtx.h states for the
+// entry of the same name. `bad`: device counter of lanes whose material /
+// emitter / prim index lay outside the scene's tables (treated as invalid,
+// never dereferenced). `op` of launch_blk_math: MTX_MATH_* (mtx.h).
+void launch_blk_seed(uint32_t n, uint32_t seed, const uint32_t *lanes, uint32_t skip, uint64_t *state, hipStream_t st);
+void launch_blk_next(uint32_t n, uint64_t *state, int dims, float *out, hipStream_t st);
+// trace != 0: closest-hit traversal of (o, d, maxt) first; else the hit
+// records (t, prim, u, v) are given.
+void launch_blk_interact(const DevScene &s, uint32_t n, int trace, const float *o, const float *d, const float *maxt,
+                         const float *t, const uint32_t *prim, const float *u, const float *v, const uint8_t *active,
+                         const mtx_si_planes &si, uint32_t *bad, hipStream_t st);
+void launch_blk_ray_test(const DevScene &s, uint32_t n, const float *o, const float *d, const float *maxt,
+                         const uint8_t *active, uint8_t *out, hipStream_t st);
+void launch_blk_spawn(uint32_t n, const float *p, const float *nrm, const float *x, int to, float *o, float *d,
+                      float *maxt, hipStream_t st);
+void launch_blk_sample_emitter(const DevScene &s, uint32_t n, const float *p, const float *nrm, const float *u,
+                               const uint8_t *active, int test_visibility, const mtx_ds_planes &ds, float *weight,
+                               hipStream_t st);
+void launch_blk_emitter(const DevScene &s, uint32_t n, const int32_t *emitter, const float *d, const float *dist,
+                        const float *nrm, const float *wi, const uint8_t *active, float *pdf, float *le,
+                        uint32_t *bad, hipStream_t st);
+void launch_blk_bsdf(const DevScene &s, uint32_t n_materials, uint32_t n, const int32_t *material, const float *uv,
+                     const float *wi, const float *wo, const float *u1, const float *u2, const uint8_t *active,
+                     const mtx_bsdf_planes &out, uint32_t *flags, uint32_t *bad, hipStream_t st);
+void launch_blk_math(int op, uint32_t n, const float *a, const float *b, const float *c, float *out, hipStream_t st);
+
+}  // namespace mtxd

@@ -6,6 +6,7 @@ primitives (prefix_sum.py, hashgrid.py, reductions.py). Host code is Python;
 every hot-path operation runs in libmtx.so (hand-written HIP for gfx950)
 through the C ABI declared in include/mtx.h.
 """
+from . import blocks  # noqa: F401
 from ._lib import MtxError, context, lib  # noqa: F401
 from .integrators import (  # noqa: F401
     IndependentSampler,

@@ -307,6 +307,23 @@ class NeradArgs(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+# Building blocks (mtx.h "building blocks"): plane sets of device pointers.
+class SiPlanes(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("p", "n", "sh_n", "uv", "wi", "t", "prim", "material", "emitter", "bary")]
+
+
+class DsPlanes(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("p", "n", "d", "dist", "pdf", "emitter")]
+
+
+class BsdfPlanes(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("value", "pdf", "s_wo", "s_pdf", "s_eta", "s_type", "weight")]
+
+
+MTX_MATH_FMA, MTX_MATH_DIV, MTX_MATH_RCP, MTX_MATH_SQRT, MTX_MATH_DOT3 = 0, 1, 2, 3, 4
+MTX_MATH_NORM3, MTX_MATH_NORMALIZE3, MTX_MATH_TO_LOCAL, MTX_MATH_TO_WORLD = 5, 6, 7, 8
+MTX_MATH_MIS_A, MTX_MATH_MIS_B = 9, 10
+
 # Every symbol include/mtx.h declares (checked by tests/test_abi.py).
 EXPORTS = [
     "mtx_abi_version",
@@ -355,4 +372,14 @@ EXPORTS = [
     "mtx_scene_update_vertices",
     "mtx_scene_read",
     "mtx_tri_area_f32",
+    "mtx_blocks_sampler_seed_dev",
+    "mtx_blocks_sampler_next_dev",
+    "mtx_blocks_ray_intersect_dev",
+    "mtx_blocks_ray_test_dev",
+    "mtx_blocks_interact_dev",
+    "mtx_blocks_spawn_dev",
+    "mtx_blocks_sample_emitter_dev",
+    "mtx_blocks_emitter_dev",
+    "mtx_blocks_bsdf_dev",
+    "mtx_blocks_math_dev",
 ]

@@ -94,6 +94,16 @@ def lib() -> C.CDLL:
         "mtx_scene_update_vertices": ([vp, vp, vp, u32, C.c_int], C.c_int),
         "mtx_scene_read": ([vp, C.c_int, vp, u64], C.c_int),
         "mtx_tri_area_f32": ([vp, u64, vp], C.c_int),
+        "mtx_blocks_sampler_seed_dev": ([vp, u64, u32, vp, u32, vp], C.c_int),
+        "mtx_blocks_sampler_next_dev": ([vp, u64, vp, C.c_int, vp], C.c_int),
+        "mtx_blocks_ray_intersect_dev": ([vp, u64, vp, vp, vp, vp, C.POINTER(_abi.SiPlanes)], C.c_int),
+        "mtx_blocks_ray_test_dev": ([vp, u64, vp, vp, vp, vp, vp], C.c_int),
+        "mtx_blocks_interact_dev": ([vp, u64, vp, vp, vp, vp, vp, vp, C.POINTER(_abi.SiPlanes)], C.c_int),
+        "mtx_blocks_spawn_dev": ([vp, u64, vp, vp, vp, C.c_int, vp, vp, vp], C.c_int),
+        "mtx_blocks_sample_emitter_dev": ([vp, u64, vp, vp, vp, vp, C.c_int, C.POINTER(_abi.DsPlanes), vp], C.c_int),
+        "mtx_blocks_emitter_dev": ([vp, u64, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "mtx_blocks_bsdf_dev": ([vp, u64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(_abi.BsdfPlanes), vp], C.c_int),
+        "mtx_blocks_math_dev": ([vp, C.c_int, u64, vp, vp, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
