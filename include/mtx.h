@@ -644,6 +644,51 @@ enum {
 };
 int mtx_blocks_math_dev(mtx_ctx *ctx, int op, uint64_t n, const float *a, const float *b, const float *c,
                         float *out);
+/* sensor.sample_ray (path.py:45-62) of the context's bound camera for the
+ * film positions pos (2, n) in pixels (pixel + jitter): o, d (3, n) =
+ * camera_ray(cam, pos / size) with the fp32 division of the fixed
+ * integrators' camera rays, and maxt (n; may be NULL) the ray's extent to the
+ * far clip, which those integrators trace with. Positions outside the film
+ * give the rays the formula gives. Masked-off lanes get zeros. */
+int mtx_blocks_sensor_ray_dev(mtx_ctx *ctx, uint64_t n, const float *pos, const uint8_t *active, float *o, float *d,
+                              float *maxt);
+/* ImageBlock.put (path.py:101): stage 1 of the film (DESIGN.md "Film") for
+ * samples the caller holds. The film is the caller's: `planes` are the
+ * contribution planes of the band of rows [y0, y1) of a film `width` wide,
+ * 8 slots x K = (2b + 1)^2 taps x band pixels float4 ([slot][K][band_px]),
+ * b = the filter's reach (mtx_rfilter_info); zeroed by the caller before the
+ * first put. Needs no scene.
+ *   A sample (pos (2, n), L (3, n)) belongs to the source pixel (floor(pos.x),
+ * floor(pos.y)). It is dropped if its lane is off, its position is not
+ * finite, or its source pixel lies outside [0, width) x [y0, y1); *dropped
+ * (host, may be NULL) receives the number dropped for the last two reasons,
+ * which is no error. Per source pixel the kept samples of the call are
+ * ranked r = 0, 1, .. by ascending lane; sample r goes to slot
+ * film_slot(sample_offset + r, T), T = spp_total, or the pixel's count in
+ * this call when spp_total = 0. The pixel's accumulators are loaded from the
+ * planes, updated in rank order by the operation sequence of the fixed
+ * integrators' film kernels, and stored back: a put split into passes of
+ * whole pixels, or into sample ranges with spp_total / sample_offset set,
+ * leaves the same planes as the single put.
+ *   pixel_major_spp = s > 0 declares the layout of a render loop: lane i
+ * belongs to pixel px0 + i / s (pixels as y * width + x; n a multiple of s;
+ * the pixels inside the band). The claim is checked on the device before any
+ * plane is written: an active lane with a finite position must have its
+ * position in that pixel, the upper edge included ((float)x + u rounds up to
+ * x + 1 for u next to 1, and such a sample stays with the pixel that drew
+ * it, as in the fixed integrators). Otherwise MTX_E_ARG with the number of
+ * such lanes, and the planes are unchanged. Non-finite positions are dropped
+ * and counted as above. Where both layouts describe the same samples
+ * (floor(pos) is the claimed pixel for every kept lane) the planes are
+ * identical. */
+int mtx_blocks_film_put_dev(mtx_ctx *ctx, float *planes, uint32_t width, uint32_t y0, uint32_t y1, uint32_t rfilter,
+                            uint64_t n, const float *pos, const float *L, const uint8_t *active, uint32_t spp_total,
+                            uint32_t sample_offset, uint32_t pixel_major_spp, uint32_t px0, uint64_t *dropped);
+/* Stage 2: the raw film (y1 - y0 + 2b) x (width + 2b) x RGBW (device) of the
+ * planes: per slot the K neighbours of a film pixel in (dy, dx) order, then
+ * the slots' fixed tree -- the layout and order of mtx_render's film. */
+int mtx_blocks_film_gather_dev(mtx_ctx *ctx, const float *planes, uint32_t width, uint32_t y0, uint32_t y1,
+                               uint32_t rfilter, float *film);
 
 /* --------------------------- film filters ------------------------- */
 /* Host-only: border (pixels on every side of the raw film) and radius of a

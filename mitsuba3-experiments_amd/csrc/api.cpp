@@ -3141,4 +3141,111 @@ int mtx_blocks_math_dev(mtx_ctx *c, int op, uint64_t n, const float *a, const fl
   return blk_end(c, fn, nullptr);
 }
 
+int mtx_blocks_sensor_ray_dev(mtx_ctx *c, uint64_t n, const float *pos, const uint8_t *active, float *o, float *d,
+                              float *maxt) {
+  const char *fn = "mtx_blocks_sensor_ray_dev";
+  int rc = blk_begin(c, fn, n, true, {pos, o, d});
+  if (rc || n == 0) return rc;
+  if ((rc = need_device(c, fn, {pos, active, o, d, maxt}))) return rc;
+  mtxd::launch_blk_sensor_ray(c->scene.camera, (uint32_t)n, pos, active, o, d, maxt, c->stream);
+  return blk_end(c, fn, nullptr);
+}
+
+}  // extern "C"
+
+// The band and filter of a caller-owned film: checked, never trusted.
+static int film_band(const char *fn, uint32_t width, uint32_t y0, uint32_t y1, uint32_t rfilter, mtxd::FilmBand *g) {
+  if (mtx::rfilter_reach(rfilter) == 0xffffffffu) {
+    mtx_set_error("%s: unknown reconstruction filter %u", fn, rfilter);
+    return MTX_E_ARG;
+  }
+  if (width == 0 || y1 <= y0 || (uint64_t)(y1 - y0) * width >= (1ull << 31) || (uint64_t)y1 * width >= (1ull << 31) ||
+      width >= (1u << 24) || y1 >= (1u << 24)) {
+    mtx_set_error("%s: bad film band (width %u, rows [%u, %u))", fn, width, y0, y1);
+    return MTX_E_ARG;
+  }
+  *g = mtxd::FilmBand{width, y0, y1, (y1 - y0) * width, rfilter};
+  return MTX_OK;
+}
+
+extern "C" {
+
+int mtx_blocks_film_put_dev(mtx_ctx *c, float *planes, uint32_t width, uint32_t y0, uint32_t y1, uint32_t rfilter,
+                            uint64_t n, const float *pos, const float *L, const uint8_t *active, uint32_t spp_total,
+                            uint32_t sample_offset, uint32_t pixel_major_spp, uint32_t px0, uint64_t *dropped) {
+  const char *fn = "mtx_blocks_film_put_dev";
+  if (dropped) *dropped = 0;
+  int rc = blk_begin(c, fn, n, false, {planes, pos, L});
+  if (rc) return rc;
+  mtxd::FilmBand g;
+  if ((rc = film_band(fn, width, y0, y1, rfilter, &g))) return rc;
+  if (n == 0) return MTX_OK;
+  if (sample_offset + n >= (1ull << 32)) {
+    mtx_set_error("%s: sample_offset + n >= 2^32", fn);
+    return MTX_E_ARG;
+  }
+  const uint32_t s = pixel_major_spp;
+  if (s) {
+    if (n % s || px0 < y0 * width || (uint64_t)px0 + n / s > (uint64_t)y1 * width) {
+      mtx_set_error("%s: pixel-major layout: n = %llu is not a multiple of %u samples, or the pixels [%u, %llu) leave "
+                    "the band", fn, (unsigned long long)n, s, px0, (unsigned long long)px0 + n / s);
+      return MTX_E_ARG;
+    }
+    if (spp_total && (uint64_t)sample_offset + s > spp_total) {
+      mtx_set_error("%s: sample_offset %u + %u samples > spp_total %u", fn, sample_offset, s, spp_total);
+      return MTX_E_ARG;
+    }
+  }
+  if ((rc = need_device(c, fn, {planes, pos, L, active})) || (rc = dalloc(c->s0, 64))) return rc;
+  uint32_t *counts = (uint32_t *)c->s0.p;
+  uint32_t h[mtxd::kPutCounters] = {0, 0, 0};
+  HIP_TRY(hipMemsetAsync(counts, 0, sizeof h, c->stream));
+  if (s) {
+    mtxd::launch_blk_film_claim(g, (uint32_t)n, pos, active, s, px0, counts, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h, counts, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (h[mtxd::kPutViolations]) {
+      mtx_set_error("%s: %u lanes whose position lies outside the pixel the pixel-major layout gives them (%u "
+                    "samples per pixel from pixel %u); the planes are unchanged", fn, h[mtxd::kPutViolations], s, px0);
+      return MTX_E_ARG;
+    }
+    mtxd::launch_blk_film_put_staged(g, (uint32_t)n, pos, L, active, s, px0, spp_total, sample_offset,
+                                     h[mtxd::kPutOff] != 0, (float4 *)planes, c->stream);
+  } else {
+    const uint32_t n_keys = g.band_px + 1;  // the last key: inactive and dropped lanes
+    if ((rc = dalloc(c->s1, 4 * n)) || (rc = dalloc(c->s2, 4ull * n_keys)) || (rc = dalloc(c->s3, 4ull * n_keys)) ||
+        (rc = dalloc(c->s4, 4 * n)) || (rc = dalloc(c->s5, mtxd::hashgrid_workspace_bytes(n, n_keys))))
+      return rc;
+    uint32_t *keys = (uint32_t *)c->s1.p, *ksize = (uint32_t *)c->s2.p, *koff = (uint32_t *)c->s3.p;
+    uint32_t *order = (uint32_t *)c->s4.p;
+    mtxd::launch_blk_film_keys(g, (uint32_t)n, pos, active, keys, counts, c->stream);
+    HIP_TRY(hipGetLastError());
+    if ((rc = mtxd::group_by_u32(keys, n, n_keys, ksize, koff, order, c->s5.p, c->stream))) return rc;
+    mtxd::launch_blk_film_put(g, (uint32_t)n, pos, L, ksize, koff, order, spp_total, sample_offset, (float4 *)planes,
+                              c->stream);
+    HIP_TRY(hipMemcpyAsync(h, counts, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  }
+  if ((rc = blk_end(c, fn, nullptr))) return rc;
+  if (dropped) *dropped = h[mtxd::kPutDropped];
+  return MTX_OK;
+}
+
+int mtx_blocks_film_gather_dev(mtx_ctx *c, const float *planes, uint32_t width, uint32_t y0, uint32_t y1,
+                               uint32_t rfilter, float *film) {
+  const char *fn = "mtx_blocks_film_gather_dev";
+  int rc = blk_begin(c, fn, 1, false, {planes, film});
+  if (rc) return rc;
+  mtxd::FilmBand g;
+  if ((rc = film_band(fn, width, y0, y1, rfilter, &g))) return rc;
+  const uint64_t b = mtx::rfilter_reach(rfilter);
+  if ((width + 2 * b) * (y1 - y0 + 2 * b) >= (1ull << 31)) {
+    mtx_set_error("%s: film too large", fn);
+    return MTX_E_ARG;
+  }
+  if ((rc = need_device(c, fn, {planes, film}))) return rc;
+  mtxd::launch_film_gather((const float4 *)planes, (float4 *)film, width, y0, y1, 8, 0xffu, rfilter, c->stream);
+  return blk_end(c, fn, nullptr);
+}
+
 }  // extern "C"

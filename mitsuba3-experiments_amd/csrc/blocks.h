@@ -35,5 +35,30 @@ void launch_blk_bsdf(const DevScene &s, uint32_t n_materials, uint32_t n, const 
                      const float *wi, const float *wo, const float *u1, const float *u2, const uint8_t *active,
                      const mtx_bsdf_planes &out, uint32_t *flags, uint32_t *bad, hipStream_t st);
 void launch_blk_math(int op, uint32_t n, const float *a, const float *b, const float *c, float *out, hipStream_t st);
+// o, d (3, n) and maxt (n, may be null) of camera_ray(cam, pos / size); masked-off lanes: zeros.
+void launch_blk_sensor_ray(const mtx_camera &cam, uint32_t n, const float *pos, const uint8_t *active, float *o,
+                           float *d, float *maxt, hipStream_t st);
+
+// Film put (mtx_blocks_film_put_dev): the band [y0, y1) of a film `width`
+// wide, its filter, and the contribution planes [slot 8][K][band_px] float4.
+struct FilmBand {
+  uint32_t width, y0, y1, band_px, rfilter;
+};
+// Words of the put's device counters.
+enum { kPutViolations = 0, kPutDropped = 1, kPutOff = 2, kPutCounters = 3 };
+// General path: keys (n) for the group-by with n_keys = band_px + 1 (the last
+// is the trash cell); then one lane per source pixel over the groups.
+void launch_blk_film_keys(const FilmBand &g, uint32_t n, const float *pos, const uint8_t *active, uint32_t *keys,
+                          uint32_t *counts, hipStream_t st);
+void launch_blk_film_put(const FilmBand &g, uint32_t n, const float *pos, const float *L, const uint32_t *key_size,
+                         const uint32_t *key_offset, const uint32_t *order, uint32_t spp_total,
+                         uint32_t sample_offset, float4 *planes, hipStream_t st);
+// Pixel-major path: the claim check (counts only), then the staged put;
+// `ragged`: the check found lanes that are off or dropped.
+void launch_blk_film_claim(const FilmBand &g, uint32_t n, const float *pos, const uint8_t *active, uint32_t s,
+                           uint32_t px0, uint32_t *counts, hipStream_t st);
+void launch_blk_film_put_staged(const FilmBand &g, uint32_t n, const float *pos, const float *L,
+                                const uint8_t *active, uint32_t s, uint32_t px0, uint32_t spp_total,
+                                uint32_t sample_offset, int ragged, float4 *planes, hipStream_t st);
 
 }  // namespace mtxd

@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "device_common.h"
+#include "film_dev.h"
 
 namespace mtxd {
 
@@ -258,6 +259,233 @@ __global__ __launch_bounds__(kBlkBlock) void k_blk_math(int op, uint32_t n, cons
   }
 }
 
+// sensor.sample_ray (path.py:45-62): camera_path's two lines (kernels.hip)
+// on a film position the caller holds.
+__global__ __launch_bounds__(kBlkBlock) void k_blk_sensor_ray(mtx_camera cam, uint32_t n, const float *pos,
+                                                              const uint8_t *active, float *o, float *d,
+                                                              float *maxt) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    Ray r;
+    r.o = r.d = v3s(0.f);
+    r.maxt = 0.f;
+    if (lane_on(active, i)) {
+      const V2 ps = ld2(pos, n, i);
+      r = camera_ray(cam, V2{ps.x / (float)cam.width, ps.y / (float)cam.height});
+    }
+    st3(o, n, i, r.o);
+    st3(d, n, i, r.d);
+    if (maxt) maxt[i] = r.maxt;
+  }
+}
+
+// ------------------------------------------------------------------ film --
+// Stage 1 of the film (DESIGN.md "Film") on samples the caller holds. The
+// contribution planes are the fused film's, [slot][K][band_px] float4; a put
+// loads a source pixel's accumulators from them, adds its samples in rank
+// order with film_accumulate (film_dev.h) and stores them back.
+
+// Walks the slots of one source pixel's samples in ascending sample index g:
+// the accumulators of a slot are loaded when its first sample arrives and
+// stored when a later slot's arrives (or at the end); slots without a sample
+// of this put are neither read nor written.
+template <int K>
+struct PutSlots {
+  float4 *planes;
+  size_t band_px, o;
+  uint32_t T, cur, end;
+  bool held;
+  __device__ __forceinline__ void init(float4 *planes_, uint32_t band_px_, uint32_t o_, uint32_t T_) {
+    planes = planes_;
+    band_px = band_px_;
+    o = o_;
+    T = T_;
+    cur = 0;
+    end = film_slot_end(0, T);
+    held = false;
+  }
+  __device__ __forceinline__ void store(const float4 *acc) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) planes[((size_t)cur * K + k) * band_px + o] = acc[k];
+  }
+  __device__ __forceinline__ void enter(uint32_t g, float4 *acc) {
+    if (g >= end) {
+      if (held) store(acc);
+      held = false;
+      while (g >= end) {  // film_slot(g, T), continued from the previous sample's slot
+        ++cur;
+        end = cur < 7 ? film_slot_end(cur, T) : 0xffffffffu;
+      }
+    }
+    if (!held) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] = planes[((size_t)cur * K + k) * band_px + o];
+      held = true;
+    }
+  }
+  __device__ __forceinline__ void finish(const float4 *acc) {
+    if (held) store(acc);
+  }
+};
+
+__device__ __forceinline__ bool finite2(V2 p) { return fabsf(p.x) < kInf && fabsf(p.y) < kInf; }
+
+// General path, pass 1: the source-pixel key of every lane for the stable
+// group-by, (y - y0) * W + x of floor(pos); an inactive lane and a dropped
+// one (non-finite position, or a source pixel outside the band: counted) get
+// the trash key band_px.
+__global__ __launch_bounds__(kBlkBlock) void k_blk_film_keys(FilmBand g, uint32_t n, const float *pos,
+                                                             const uint8_t *active, uint32_t *keys,
+                                                             uint32_t *counts) {
+  uint32_t dropped = 0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    uint32_t key = g.band_px;
+    if (lane_on(active, i)) {
+      const V2 ps = ld2(pos, n, i);
+      const float fx = floorf(ps.x), fy = floorf(ps.y);
+      if (finite2(ps) && fx >= 0.f && fx < (float)g.width && fy >= (float)g.y0 && fy < (float)g.y1)
+        key = ((uint32_t)fy - g.y0) * g.width + (uint32_t)fx;
+      else
+        ++dropped;
+    }
+    keys[i] = key;
+  }
+  if (dropped) atomicAdd(counts + kPutDropped, dropped);
+}
+
+// General path, pass 2: one lane per source pixel walks the pixel's lanes in
+// the group-by's order (ascending lane index).
+template <int N, uint32_t F>
+__global__ __launch_bounds__(film_max_block(N)) void k_blk_film_put(FilmBand g, uint32_t n, const float *pos,
+                                                                    const float *L, const uint32_t *key_size,
+                                                                    const uint32_t *key_offset, const uint32_t *order,
+                                                                    uint32_t spp_total, uint32_t sample_offset,
+                                                                    float4 *planes) {
+  constexpr int K = film_taps(N);
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= g.band_px) return;
+  const uint32_t cnt = key_size[q];
+  if (cnt == 0) return;
+  const uint32_t off = key_offset[q];
+  const uint32_t row = q / g.width;
+  const int y = (int)(g.y0 + row), x = (int)(q - row * g.width);
+  PutSlots<K> slots;
+  slots.init(planes, g.band_px, q, spp_total ? spp_total : cnt);
+  float4 acc[K];
+  for (uint32_t r = 0; r < cnt; ++r) {
+    const uint32_t i = order[off + r];
+    slots.enter(sample_offset + r, acc);
+    const V2 ps = ld2(pos, n, i);
+    film_accumulate<N, F>(acc, x, y, make_float2(ps.x, ps.y), ld3(L, n, i));
+  }
+  slots.finish(acc);
+}
+
+// Pixel-major path, pass 1: lane i claims pixel px0 + i / s. An active lane
+// with a finite position keeps the claim when floor(pos) is that pixel, or
+// pos lies exactly on the pixel's upper edge: (float)x + u rounds up to x + 1
+// for u close to 1, and the fixed integrators keep such a sample in the
+// pixel that drew it (mtx_core/film.h, the box filter's closed interval).
+// counts: violations, dropped (non-finite), lanes that are not kept.
+__global__ __launch_bounds__(kBlkBlock) void k_blk_film_claim(FilmBand g, uint32_t n, const float *pos,
+                                                              const uint8_t *active, uint32_t s, uint32_t px0,
+                                                              uint32_t *counts) {
+  uint32_t bad = 0, dropped = 0, off = 0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    if (!lane_on(active, i)) {
+      ++off;
+      continue;
+    }
+    const V2 ps = ld2(pos, n, i);
+    if (!finite2(ps)) {
+      ++dropped;
+      ++off;
+      continue;
+    }
+    const uint32_t pix = px0 + i / s, y = pix / g.width, x = pix - y * g.width;
+    const float fx = (float)x, fy = (float)y;
+    const bool in_x = floorf(ps.x) == fx || ps.x == fx + 1.f, in_y = floorf(ps.y) == fy || ps.y == fy + 1.f;
+    if (!in_x || !in_y) ++bad;
+  }
+  if (bad) atomicAdd(counts + kPutViolations, bad);
+  if (dropped) atomicAdd(counts + kPutDropped, dropped);
+  if (off) atomicAdd(counts + kPutOff, off);
+}
+
+// Pixel-major path, pass 2 (after a clean pass 1): a wave stages 64 pixels x
+// S samples of the five planes through LDS, so every global read is a run of
+// whole lines (the planes are (C, n): the 64 x s floats of the wave's pixels
+// are contiguous in each); then each lane accumulates its own pixel in
+// sample order. S = min(s, kPutStage); rows of S | 1 words keep the
+// per-lane column reads on distinct banks. A lane that is off or dropped is
+// staged as a NaN in the x plane and skipped. `ragged`: some lane of the put
+// is not kept, so without spp_total a pixel's T is its own kept count,
+// taken in a first sweep over the position planes.
+constexpr int kPutStage = 16;
+
+template <int N, uint32_t F>
+__global__ __launch_bounds__(64) void k_blk_film_put_staged(FilmBand g, uint32_t n, const float *pos, const float *L,
+                                                            const uint8_t *active, uint32_t s, uint32_t px0,
+                                                            uint32_t n_px, uint32_t spp_total, uint32_t sample_offset,
+                                                            int ragged, float4 *planes) {
+  constexpr int K = film_taps(N);
+  extern __shared__ float put_lds[];  // 5 planes (pos.xy, L.xyz) of 64 rows, sized by the launch
+  const uint32_t S = min(s, (uint32_t)kPutStage), rowlen = S | 1u, plane = 64 * rowlen;
+  float *const sv0 = put_lds, *const sv1 = sv0 + plane, *const sv2 = sv1 + plane, *const sv3 = sv2 + plane,
+               *const sv4 = sv3 + plane;
+  const uint32_t q0 = blockIdx.x * 64, lane = threadIdx.x, q = q0 + lane;
+  const uint32_t n_here = min(64u, n_px - q0);
+  const bool live = q < n_px;
+  const uint32_t pix = px0 + q, yy = pix / g.width;
+  const int y = (int)yy, x = (int)(pix - yy * g.width);
+  const float nan = __int_as_float(0x7fc00000);
+  uint32_t T = spp_total ? spp_total : s;
+  if (ragged && !spp_total) {
+    T = 0;
+    for (uint32_t s0 = 0; s0 < s; s0 += S) {
+      const uint32_t ns = min(S, s - s0);
+      for (uint32_t e = lane; e < n_here * ns; e += 64) {
+        const uint32_t j = e / ns, sm = e - j * ns;
+        const uint32_t i = (q0 + j) * s + s0 + sm;
+        sv0[j * rowlen + sm] = lane_on(active, i) && finite2(ld2(pos, n, i)) ? 0.f : nan;
+      }
+      __syncthreads();
+      if (live)
+        for (uint32_t sm = 0; sm < ns; ++sm) T += sv0[lane * rowlen + sm] == 0.f ? 1u : 0u;
+      __syncthreads();
+    }
+  }
+  PutSlots<K> slots;
+  slots.init(planes, g.band_px, live ? pix - g.y0 * g.width : 0u, T);
+  float4 acc[K];
+  uint32_t rank = 0;
+  for (uint32_t s0 = 0; s0 < s; s0 += S) {
+    const uint32_t ns = min(S, s - s0);
+    for (uint32_t e = lane; e < n_here * ns; e += 64) {
+      const uint32_t j = e / ns, sm = e - j * ns;
+      const uint32_t i = (q0 + j) * s + s0 + sm, a = j * rowlen + sm;
+      const V2 ps = ld2(pos, n, i);
+      const V3 l = ld3(L, n, i);
+      sv0[a] = lane_on(active, i) && finite2(ps) ? ps.x : nan;
+      sv1[a] = ps.y;
+      sv2[a] = l.x;
+      sv3[a] = l.y;
+      sv4[a] = l.z;
+    }
+    __syncthreads();
+    if (live)
+      for (uint32_t sm = 0; sm < ns; ++sm) {
+        const uint32_t a = lane * rowlen + sm;
+        const float sx = sv0[a];
+        if (sx != sx) continue;
+        slots.enter(sample_offset + rank, acc);
+        ++rank;
+        film_accumulate<N, F>(acc, x, y, make_float2(sx, sv1[a]), V3{sv2[a], sv3[a], sv4[a]});
+      }
+    __syncthreads();
+  }
+  if (live) slots.finish(acc);
+}
+
 inline unsigned blk_grid(uint32_t n, int block) {
   // enough blocks to fill the chip several times over; the loops stride
   return std::max(1u, std::min<unsigned>((n + block - 1) / block, 256u * 32u));
@@ -325,6 +553,64 @@ void launch_blk_bsdf(const DevScene &s, uint32_t n_materials, uint32_t n, const 
 }
 void launch_blk_math(int op, uint32_t n, const float *a, const float *b, const float *c, float *out, hipStream_t st) {
   hipLaunchKernelGGL(k_blk_math, dim3(blk_grid(n, kBlkBlock)), dim3(kBlkBlock), 0, st, op, n, a, b, c, out);
+}
+void launch_blk_sensor_ray(const mtx_camera &cam, uint32_t n, const float *pos, const uint8_t *active, float *o,
+                           float *d, float *maxt, hipStream_t st) {
+  hipLaunchKernelGGL(k_blk_sensor_ray, dim3(blk_grid(n, kBlkBlock)), dim3(kBlkBlock), 0, st, cam, n, pos, active, o, d,
+                     maxt);
+}
+void launch_blk_film_keys(const FilmBand &g, uint32_t n, const float *pos, const uint8_t *active, uint32_t *keys,
+                          uint32_t *counts, hipStream_t st) {
+  hipLaunchKernelGGL(k_blk_film_keys, dim3(blk_grid(n, kBlkBlock)), dim3(kBlkBlock), 0, st, g, n, pos, active, keys,
+                     counts);
+}
+void launch_blk_film_claim(const FilmBand &g, uint32_t n, const float *pos, const uint8_t *active, uint32_t s,
+                           uint32_t px0, uint32_t *counts, hipStream_t st) {
+  hipLaunchKernelGGL(k_blk_film_claim, dim3(blk_grid(n, kBlkBlock)), dim3(kBlkBlock), 0, st, g, n, pos, active, s, px0,
+                     counts);
+}
+template <int N, uint32_t F>
+static void launch_blk_film_put_t(const FilmBand &g, uint32_t n, const float *pos, const float *L,
+                                  const uint32_t *key_size, const uint32_t *key_offset, const uint32_t *order,
+                                  uint32_t spp_total, uint32_t sample_offset, float4 *planes, hipStream_t st) {
+  hipLaunchKernelGGL((k_blk_film_put<N, F>), dim3((g.band_px + 127) / 128), dim3(128), 0, st, g, n, pos, L, key_size,
+                     key_offset, order, spp_total, sample_offset, planes);
+}
+void launch_blk_film_put(const FilmBand &g, uint32_t n, const float *pos, const float *L, const uint32_t *key_size,
+                         const uint32_t *key_offset, const uint32_t *order, uint32_t spp_total,
+                         uint32_t sample_offset, float4 *planes, hipStream_t st) {
+  if (g.rfilter == MTX_RFILTER_BOX)
+    launch_blk_film_put_t<0, MTX_RFILTER_BOX>(g, n, pos, L, key_size, key_offset, order, spp_total, sample_offset,
+                                              planes, st);
+  else if (g.rfilter == MTX_RFILTER_GAUSSIAN)
+    launch_blk_film_put_t<2, MTX_RFILTER_GAUSSIAN>(g, n, pos, L, key_size, key_offset, order, spp_total,
+                                                   sample_offset, planes, st);
+  else
+    launch_blk_film_put_t<1, MTX_RFILTER_TENT>(g, n, pos, L, key_size, key_offset, order, spp_total, sample_offset,
+                                               planes, st);
+}
+template <int N, uint32_t F>
+static void launch_blk_film_put_staged_t(const FilmBand &g, uint32_t n, const float *pos, const float *L,
+                                         const uint8_t *active, uint32_t s, uint32_t px0, uint32_t spp_total,
+                                         uint32_t sample_offset, int ragged, float4 *planes, hipStream_t st) {
+  const uint32_t n_px = n / s;
+  // 5 planes x 64 rows of min(s, kPutStage) | 1 words: 3.8 KB at s = 3, 11.5 KB at 8 or 9, 21.8 KB from 16 on
+  const size_t lds = 5 * 64 * (size_t)(std::min<uint32_t>(s, kPutStage) | 1u) * sizeof(float);
+  hipLaunchKernelGGL((k_blk_film_put_staged<N, F>), dim3((n_px + 63) / 64), dim3(64), lds, st, g, n, pos, L, active, s,
+                     px0, n_px, spp_total, sample_offset, ragged, planes);
+}
+void launch_blk_film_put_staged(const FilmBand &g, uint32_t n, const float *pos, const float *L,
+                                const uint8_t *active, uint32_t s, uint32_t px0, uint32_t spp_total,
+                                uint32_t sample_offset, int ragged, float4 *planes, hipStream_t st) {
+  if (g.rfilter == MTX_RFILTER_BOX)
+    launch_blk_film_put_staged_t<0, MTX_RFILTER_BOX>(g, n, pos, L, active, s, px0, spp_total, sample_offset, ragged,
+                                                     planes, st);
+  else if (g.rfilter == MTX_RFILTER_GAUSSIAN)
+    launch_blk_film_put_staged_t<2, MTX_RFILTER_GAUSSIAN>(g, n, pos, L, active, s, px0, spp_total, sample_offset,
+                                                          ragged, planes, st);
+  else
+    launch_blk_film_put_staged_t<1, MTX_RFILTER_TENT>(g, n, pos, L, active, s, px0, spp_total, sample_offset, ragged,
+                                                      planes, st);
 }
 
 }  // namespace mtxd

@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "device_common.h"
+#include "film_dev.h"
 #include "mtx_core/film.h"
 #include "restir_dev.h"
 
@@ -1549,32 +1550,8 @@ __device__ __forceinline__ V3 final_L(const WaveBuffers &b, const ChunkParams &p
 // lane accumulates its own pixel in sample order (same order as below).
 constexpr int kFilmStage = 8;  // 8 (11.5 KB of LDS per wave, twice the waves per CU) beat 16 by 0.8 ms, and 4
 
-constexpr int film_taps(int N) { return (2 * N + 1) * (2 * N + 1); }
-// Block-size bound of the per-pixel kernels launched with 128 threads: the
-// gaussian's 25 float4 accumulators need more than the 128 VGPRs the default
-// bound (1024 threads) leaves a lane; the tent and the box keep the default.
-constexpr int film_max_block(int N) { return N == 2 ? 128 : 1024; }
-
-template <int N, uint32_t F>
-__device__ __forceinline__ void film_accumulate(float4 *acc, int x, int y, float2 ps, V3 L) {
-  constexpr int D = 2 * N + 1;
-  float wxs[D];
-#pragma unroll
-  for (int dx = 0; dx < D; ++dx) wxs[dx] = rfilter_eval(F, ps.x - ((float)(x + dx - N) + 0.5f));
-#pragma unroll
-  for (int dy = 0; dy < D; ++dy) {
-    const float wy = rfilter_eval(F, ps.y - ((float)(y + dy - N) + 0.5f));
-#pragma unroll
-    for (int dx = 0; dx < D; ++dx) {
-      const float w = wxs[dx] * wy;
-      float4 &c = acc[dy * D + dx];
-      c.x = c.x + L.x * w;
-      c.y = c.y + L.y * w;
-      c.z = c.z + L.z * w;
-      c.w = c.w + w;
-    }
-  }
-}
+// film_taps, film_max_block and film_accumulate (the splat of one sample):
+// film_dev.h, shared with the building blocks' film put (blocks.hip).
 
 // Partial film slots (mtx_core/common.h film_slot): with p.film_slots == 8
 // a lane moves on to the next slot's contribution planes whenever its sample

@@ -382,4 +382,7 @@ EXPORTS = [
     "mtx_blocks_emitter_dev",
     "mtx_blocks_bsdf_dev",
     "mtx_blocks_math_dev",
+    "mtx_blocks_sensor_ray_dev",
+    "mtx_blocks_film_put_dev",
+    "mtx_blocks_film_gather_dev",
 ]

@@ -21,6 +21,13 @@ values and never reaches a traversal. Plain ``+ - * < min max where`` stay
 torch operations (each is one IEEE operation); everything whose rounding torch
 does not pin -- fused multiply-add, division, square root, dot products, frame
 transforms, the MIS weights -- goes through the exact helpers below.
+
+Around a ``sample()`` written this way, :class:`Sensor` (``sensor.sample_ray``),
+:class:`Film` (``ImageBlock.put`` and the film's fixed order, on planes the
+caller owns) and :class:`SamplingIntegrator` (the render loop of
+path.py:103-192; ``mtx.register_integrator`` / ``mtx.load_dict`` take a
+subclass) make it a renderer whose raw film equals the fused integrator's
+bit for bit when the loop restates that integrator.
 """
 from __future__ import annotations
 
@@ -470,3 +477,232 @@ class Scene:
             check(lib().mtx_blocks_bsdf_dev(self._call(dev), n, si.material.data_ptr(), None, None, None, None, None,
                                             None, None, out.data_ptr()), "mtx_blocks_bsdf_dev")
         return out
+
+
+# ------------------------------------------------------------------ sensor --
+
+class Ray:
+    """A wavefront of rays: o, d (3, N) and maxt (N; None = unbounded)."""
+
+    def __init__(self, o, d, maxt=None):
+        self.o, self.d, self.maxt = o, d, maxt
+
+
+def _mtx_scene(scene):
+    from .integrators import mtx_scene_of
+
+    return scene.scene if isinstance(scene, Scene) else mtx_scene_of(scene)
+
+
+class Sensor:
+    """The scene's camera, or `sensor` in any form :func:`mtx.scene_with_sensor`
+    takes (an ``mtx_camera``, ``Scene.sensors()[i]``, a perspective sensor
+    dictionary, ...), with the reference's ``sensor.sample_ray`` on CUDA
+    tensors (path.py:45-62)."""
+
+    def __init__(self, scene, sensor=None, device=None):
+        from .integrators import _bind_scene, scene_with_sensor
+
+        self.scene = scene_with_sensor(_mtx_scene(scene), sensor)
+        self.ctx = context(device)
+        self._bind = _bind_scene
+        self._bind(self.ctx, self.scene)
+
+    @property
+    def width(self) -> int:
+        return int(self.scene.width)
+
+    @property
+    def height(self) -> int:
+        return int(self.scene.height)
+
+    def sample_ray(self, pos, active=None) -> Ray:
+        """Rays through the film positions pos (2, N) in pixels (pixel +
+        jitter, path.py:45): camera_ray(pos / size), the camera rays of the
+        fixed integrators. ``maxt`` reaches the far clip, as theirs does.
+        Masked-off lanes get zeros."""
+        torch = _torch()
+        n = _f32("sample_ray: pos", pos, 2, None)
+        dev = pos.device
+        _, am = _mask("sample_ray: active", active, n, dev)
+        o, d, maxt = _empty(dev, 3, n), _empty(dev, 3, n), _empty(dev, None, n)
+        if n:
+            idx = dev.index if dev.index is not None else torch.cuda.current_device()
+            if idx != self.ctx.device:
+                raise MtxError(f"tensors on cuda:{idx}, the sensor is bound to cuda:{self.ctx.device}")
+            torch.cuda.current_stream(dev).synchronize()  # libmtx runs on its own stream
+            self._bind(self.ctx, self.scene)
+            check(lib().mtx_blocks_sensor_ray_dev(self.ctx.handle, n, pos.data_ptr(), am, o.data_ptr(), d.data_ptr(),
+                                                  maxt.data_ptr()), "mtx_blocks_sensor_ray_dev")
+        return Ray(o, d, maxt)
+
+
+# -------------------------------------------------------------------- film --
+
+def _rfilter_id(rfilter) -> int:
+    fid = _abi.RFILTERS.get(rfilter, rfilter)
+    if fid not in _abi.RFILTER_BORDER:
+        raise MtxError(f"unknown reconstruction filter {rfilter!r}; supported: {sorted(_abi.RFILTERS)}")
+    return fid
+
+
+def develop(raw, border: int):
+    """hdrfilm develop of a raw film tensor (rows + 2b, W + 2b, 4): the inner
+    pixels, RGB / weight by the exact division (0 where the weight is 0)."""
+    torch = _torch()
+    border = int(border)
+    if border < 0 or 2 * border >= min(raw.shape[0], raw.shape[1]):
+        raise MtxError(f"border {border} does not fit a film of shape {tuple(raw.shape)}")
+    inner = raw[border: raw.shape[0] - border, border: raw.shape[1] - border]
+    w = inner[..., 3:4]
+    lit = w != 0
+    rgb = div(inner[..., :3].contiguous(), torch.where(lit, w, torch.ones_like(w)).expand(-1, -1, 3).contiguous())
+    return torch.where(lit, rgb, torch.zeros_like(rgb))
+
+
+class Film:
+    """The film of rows [y0, y1) of an image `width` wide, filled by
+    :meth:`put` (ImageBlock.put, path.py:101) and read by :meth:`raw` /
+    :meth:`develop`: the two stages and the fixed order of the fixed
+    integrators' film (DESIGN.md "Film"), so equal samples give equal bits.
+    The state is ``planes``, a zeroed (8, K, band pixels, 4) tensor: 8 partial
+    slots x K = (2b + 1)^2 taps of the filter (b = its reach)."""
+
+    def __init__(self, width: int, y0: int, y1: int, rfilter="tent", device=None):
+        torch = _torch()
+        self.rfilter = _rfilter_id(rfilter)
+        self.border = _abi.RFILTER_BORDER[self.rfilter]
+        self.width, self.y0, self.y1 = int(width), int(y0), int(y1)
+        if self.width <= 0 or self.y0 < 0 or self.y1 <= self.y0:
+            raise MtxError(f"Film: bad band (width {width}, rows [{y0}, {y1}))")
+        if not torch.cuda.is_available():
+            raise MtxError("blocks.Film: no GPU (the blocks have no CPU fallback)")
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+        self.band_px = (self.y1 - self.y0) * self.width
+        self.planes = torch.zeros((8, (2 * self.border + 1) ** 2, self.band_px, 4), dtype=torch.float32,
+                                  device=self.device)
+
+    def put(self, pos, L, active=None, spp_total=None, sample_offset: int = 0, pixel_major_spp: int = 0,
+            px0: int | None = None) -> int:
+        """Splat the samples (pos (2, N) in pixels, L (3, N)) and return how
+        many were dropped for a non-finite position or a source pixel
+        (floor(pos)) outside the band; inactive lanes are skipped silently.
+
+        Per source pixel the call's kept samples, in ascending lane order,
+        are samples ``sample_offset + 0, 1, ..`` of ``spp_total`` (None: the
+        pixel's count in this call) and fall into the 8 slots accordingly;
+        the accumulators continue from the planes. So passes of whole
+        pixels, and sample ranges with ``spp_total`` / ``sample_offset``,
+        leave the planes of the single put.
+
+        ``pixel_major_spp = s``: lane i belongs to pixel ``px0 + i // s``
+        (y * width + x; default px0: the band's first pixel), the layout of
+        a render loop. No grouping pass then; the claim is verified on the
+        device first, and a false one raises with the planes unchanged."""
+        n = _f32("put: pos", pos, 2, None)
+        dev = pos.device
+        _f32("put: L", L, 3, n, dev)
+        _, am = _mask("put: active", active, n, dev)
+        if dev != self.planes.device:
+            raise MtxError(f"put: pos: on {dev}, the film is on {self.planes.device}")
+        s = int(pixel_major_spp)
+        if s < 0 or int(sample_offset) < 0 or (spp_total is not None and int(spp_total) <= 0):
+            raise MtxError("put: pixel_major_spp, sample_offset >= 0 and spp_total > 0 expected")
+        if n == 0:
+            return 0
+        dropped = C.c_uint64(0)
+        check(lib().mtx_blocks_film_put_dev(_ctx_of(dev).handle, self.planes.data_ptr(), self.width, self.y0, self.y1,
+                                            self.rfilter, n, pos.data_ptr(), L.data_ptr(), am, int(spp_total or 0),
+                                            int(sample_offset), s, int(self.y0 * self.width if px0 is None else px0),
+                                            C.byref(dropped)), "mtx_blocks_film_put_dev")
+        return int(dropped.value)
+
+    def raw(self):
+        """The raw film (rows + 2b, W + 2b, 4) RGBW: mtx_render's layout and order."""
+        torch = _torch()
+        b = self.border
+        out = torch.empty((self.y1 - self.y0 + 2 * b, self.width + 2 * b, 4), dtype=torch.float32, device=self.device)
+        check(lib().mtx_blocks_film_gather_dev(_ctx_of(self.device).handle, self.planes.data_ptr(), self.width,
+                                               self.y0, self.y1, self.rfilter, out.data_ptr()),
+              "mtx_blocks_film_gather_dev")
+        return out
+
+    def develop(self):
+        """(rows, W, 3): the border cropped, RGB / weight."""
+        return develop(self.raw(), self.border)
+
+
+# -------------------------------------------------------------- integrator --
+
+class SamplingIntegrator:
+    """Base class of an integrator written on the blocks. Override
+    :meth:`sample`; :meth:`render_film` / :meth:`render` are the reference's
+    render loop (path.py:103-192) on device tensors: per pass the lane ids
+    ``pixel * spp_total + sample_offset + s``, a :class:`Sampler` seeded with
+    them, ``next_2d`` as the film jitter, ``Sensor.sample_ray``, ``sample()``
+    with the sampler after those two draws, ``Film.put``. A subclass that
+    restates a fixed integrator renders that integrator's raw film bit for
+    bit. Register one with ``mtx.register_integrator(name, Cls)`` and load it
+    with ``mtx.load_dict({"type": name, ...})``."""
+
+    name = ""
+
+    def __init__(self, props=None):
+        from .integrators import Properties
+
+        self.props = Properties(props or {})
+        self.rfilter = self.props.get("rfilter", "tent")  # "tent", "box", "gaussian" or "scene"
+
+    def rfilter_id(self, scene, rfilter=None) -> int:
+        """As the fixed integrators' ``rfilter_id``: the argument, else the
+        ``rfilter`` property; "scene" = the filter the scene's film declares."""
+        from .integrators import SamplingIntegrator as Fixed
+
+        return Fixed.rfilter_id(self, _mtx_scene(scene), rfilter)
+
+    def sample(self, scene, sampler, ray, medium=None, active=None):
+        """-> (L (3, N), valid (N), aovs). scene: :class:`Scene`, sampler:
+        :class:`Sampler`, ray: ``.o`` / ``.d`` (3, N) and ``.maxt`` (N)."""
+        raise NotImplementedError(f"{type(self).__name__} does not override sample()")
+
+    def render_film(self, scene, seed: int = 0, spp: int = 1, y0: int = 0, y1: int | None = None,
+                    spp_total: int | None = None, sample_offset: int = 0, sensor=None, rfilter=None,
+                    max_lanes: int | None = None):
+        """The raw film tensor of rows [y0, y1) (see the fixed integrators'
+        ``render_film``). ``max_lanes``: at most that many lanes per pass
+        (whole pixels, at least one); the film does not depend on it."""
+        torch = _torch()
+        fid = self.rfilter_id(scene, rfilter)  # an unknown filter is refused before anything is bound or launched
+        sens = Sensor(scene, sensor)
+        scn = Scene(sens.scene, sens.ctx.device)
+        W, H = sens.width, sens.height
+        y0, y1 = int(y0), int(H if y1 is None else y1)
+        spp, T, off = int(spp), int(spp_total or spp), int(sample_offset)
+        if spp <= 0 or not 0 <= y0 < y1 <= H or off < 0 or T < off + spp:
+            raise MtxError("render_film: bad rows / spp arguments")
+        film = Film(W, y0, y1, fid, sens.ctx.device)
+        dev = film.device
+        n_px = (y1 - y0) * W
+        per_pass = n_px if max_lanes is None else max(1, int(max_lanes) // spp)
+        smp = torch.arange(spp, dtype=torch.int64, device=dev)
+        for p0 in range(0, n_px, per_pass):
+            pix = torch.arange(y0 * W + p0, y0 * W + min(n_px, p0 + per_pass), dtype=torch.int64, device=dev)
+            pix = pix.repeat_interleave(spp)
+            lanes = (pix * T + off + smp.repeat(len(pix) // spp)) & 0xffffffff
+            lanes = torch.where(lanes >= 2 ** 31, lanes - 2 ** 32, lanes).to(torch.int32)  # uint32 bit patterns
+            sampler = Sampler(seed, lanes)
+            u = sampler.next_2d()  # the film jitter (path.py:45)
+            pos = torch.stack([(pix % W).to(torch.float32) + u[0], (pix // W).to(torch.float32) + u[1]])
+            ray = sens.sample_ray(pos)
+            L, _valid, _aovs = self.sample(scn, sampler, ray, None, None)
+            film.put(pos, L.contiguous(), spp_total=T, sample_offset=off, pixel_major_spp=spp, px0=y0 * W + p0)
+        return film.raw()
+
+    def render(self, scene, sensor=None, seed: int = 0, spp: int = 1, develop: bool = True, evaluate: bool = True,
+               rfilter=None):
+        """SamplingIntegrator.render (path.py:103-192): the (H, W, 3) image
+        tensor, or the raw film with develop=False."""
+        raw = self.render_film(scene, seed=seed, spp=spp, sensor=sensor, rfilter=rfilter)
+        if not develop:
+            return raw
+        return globals()["develop"](raw, _abi.RFILTER_BORDER[self.rfilter_id(scene, rfilter)])

@@ -28,7 +28,12 @@ _REGISTRY: dict = {}
 
 
 def register_integrator(name: str, ctor) -> None:
-    """Mirror of mi.register_integrator (path.py:305)."""
+    """Mirror of mi.register_integrator (path.py:305). `ctor`: a callable of
+    the properties dictionary -- ``lambda props: Cls(props)`` or the class
+    itself, a fixed integrator's or a :class:`mtx.blocks.SamplingIntegrator`
+    subclass written in Python on the blocks."""
+    if not callable(ctor):
+        raise MtxError(f"register_integrator({name!r}): expected a class or a callable of the properties")
     _REGISTRY[name] = ctor
 
 
@@ -726,7 +731,11 @@ def register_with_mitsuba(mi=None) -> bool:
         except Exception:
             return False
     _wrap_loaders(mi)
+    from .blocks import SamplingIntegrator as BlocksIntegrator
+
     for name, ctor in list(_REGISTRY.items()):
+        if isinstance(ctor, type) and issubclass(ctor, BlocksIntegrator):
+            continue  # integrators written on mtx.blocks work on torch tensors: mtx.load_dict only
         mi.register_integrator(name, _mitsuba_plugin(mi, name, ctor))
     return True
 

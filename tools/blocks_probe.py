@@ -13,7 +13,13 @@
   same rays, in Mpaths/s: the price of one launch per block and of state
   that passes through HBM between blocks.
 
-Usage: python tools/blocks_probe.py [--log2n 22] [--reps 5] [--scenes small,full] [--out profiles/blocks_probe.json]
+With ``--only film`` the document (profiles/blocks_film_probe.json) holds
+instead: ``sensor.sample_ray``, ``Film.put`` on the pixel-major and on the
+general path and ``Film.raw`` at N lanes beside torch's ``copy_`` of the same
+contribution planes, and a whole ``render_film`` composed on the blocks
+against the fused integrator's on the same frame.
+
+Usage: python tools/blocks_probe.py [--only blocks|film] [--log2n 22] [--reps 5] [--scenes small,full] [--out FILE]
 """
 import argparse
 import json
@@ -119,23 +125,92 @@ def probe_scene(label, sc, n, reps):
                          "results_bit_identical": same}}
 
 
+FILM_SPP = 8  # samples per pixel of the film probe: one per slot, every slot's planes move
+
+
+def probe_film(label, sc, n, reps):
+    """Sensor rays, Film.put on both source paths and Film.raw at n lanes (a
+    film of n / FILM_SPP pixels, pixel-major jittered positions) beside torch's
+    copy_ of the same contribution planes, and a whole render_film composed on
+    the blocks against the fused integrator's on the same frame."""
+    import blocks_integrators as bi
+    import torch
+    from mtx import blocks, load_dict
+
+    n_px = n // FILM_SPP
+    W = 1 << ((n_px.bit_length() - 1 + 1) // 2)
+    H = n_px // W
+    scf = sc.with_film(W, H)
+    sens = blocks.Sensor(scf)
+    pix = torch.arange(n_px, device="cuda").repeat_interleave(FILM_SPP)
+    g = torch.Generator(device="cuda").manual_seed(5)
+    u = torch.rand((2, n), device="cuda", generator=g) * 0.999
+    pos = torch.stack([(pix % W).float() + u[0], (pix // W).float() + u[1]])
+    L = torch.rand((3, n), device="cuda", generator=g)
+    rows = [row("sensor.sample_ray", timed(lambda: sens.sample_ray(pos), reps), n, 36)]
+    same_planes = True
+    for rf in ("tent", "gaussian"):
+        film = blocks.Film(W, 0, H, rf)
+        other = torch.empty_like(film.planes)
+        plane_bytes = film.planes.numel() * 4
+        per_lane = 2 * plane_bytes // n  # every slot's accumulators are loaded and stored once
+        rows += [
+            row(f"torch copy_ of the planes ({rf})", timed(lambda: other.copy_(film.planes), reps), n, per_lane),
+            row(f"film.put pixel-major ({rf}; claim pass + staged put)",
+                timed(lambda: film.put(pos, L, pixel_major_spp=FILM_SPP), reps), n, per_lane + 28),
+            row(f"film.put general ({rf}; keys + group-by + put)", timed(lambda: film.put(pos, L), reps), n,
+                per_lane + 28),
+            row(f"film.raw ({rf})", timed(film.raw, reps), n,
+                (plane_bytes + 16 * (W + 2 * film.border) * (H + 2 * film.border)) // n),
+        ]
+        a, b = blocks.Film(W, 0, H, rf), blocks.Film(W, 0, H, rf)
+        a.put(pos, L)
+        b.put(pos, L, pixel_major_spp=FILM_SPP)
+        same_planes = same_planes and bool(torch.equal(a.planes, b.planes))
+        del film, other, a, b
+
+    class PathMis(blocks.SamplingIntegrator):
+        def sample(self, scene, sampler, ray, medium=None, active=None):
+            Lr, valid = bi.path_mis(scene, sampler, ray.o, ray.d, 8, 2)
+            return Lr, valid, []
+
+    fused_i = load_dict({"type": "path_test", "max_depth": 8, "rr_depth": 2})
+    out = torch.empty((H + 2, W + 2, 4), device="cuda")
+    k = max(3, reps // 2)
+    fused = timed(lambda: fused_i.render_film(scf, seed=1, spp=FILM_SPP, out=out), k, 1)
+    comp = timed(lambda: PathMis().render_film(scf, seed=1, spp=FILM_SPP), k, 1)
+    same = bool(torch.equal(PathMis().render_film(scf, seed=1, spp=FILM_SPP),
+                            fused_i.render_film(scf, seed=1, spp=FILM_SPP, out=out)))
+    return {"scene": label, "n_tris": int(sc.n_tris), "lanes": n, "film": [W, H], "spp": FILM_SPP, "blocks": rows,
+            "both_paths_same_planes": same_planes,
+            "render_film": {"fused": fused, "composed_on_blocks": comp,
+                            "fused_over_composed": round(comp["median_ms"] / fused["median_ms"], 2),
+                            "films_bit_identical": same}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2n", type=int, default=22)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--scenes", default="small,full")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "blocks_probe.json"))
+    ap.add_argument("--only", default="blocks", choices=["blocks", "film"],
+                    help="blocks: the per-block rows and the composed sample(); film: sensor rays, Film.put / raw "
+                         "and the composed render_film (default --out: profiles/blocks_film_probe.json)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "blocks_probe.json" if a.only == "blocks" else "blocks_film_probe.json")
     import torch
     from mtx import scene
 
     if not torch.cuda.is_available():
         raise SystemExit("blocks_probe: needs a GPU (no time is reported from a CPU)")
-    doc = {"probe": "blocks", "hbm_peak_GBps": HBM_PEAK_GBS, "timing": "host clock around calls that end in a device "
+    doc = {"probe": a.only if a.only == "blocks" else "blocks film", "hbm_peak_GBps": HBM_PEAK_GBS,
+           "timing": "host clock around calls that end in a device "
            "synchronise; medians of --reps calls after warm-up", "scenes": []}
     for label in a.scenes.split(","):
         sc = scene.bedroom(width=64, height=36, scale=0.02, tex_res=64) if label == "small" else scene.bedroom()
-        doc["scenes"].append(probe_scene(label, sc, 1 << a.log2n, a.reps))
+        doc["scenes"].append((probe_scene if a.only == "blocks" else probe_film)(label, sc, 1 << a.log2n, a.reps))
         with open(a.out, "w") as f:  # after each scene: a later failure keeps what was measured
             json.dump(doc, f, indent=1)
             f.write("\n")
