@@ -529,8 +529,9 @@ int mtx_trace_dev(mtx_ctx *ctx, uint64_t n, const float *rays, int any_hit, uint
  * items is one contiguous (C, n) array, component c of item i at [c * n + i];
  * masks are n bytes (0 = off). A host pointer is refused (MTX_E_ARG). Work
  * runs on the context's stream and is complete on return; the caller orders
- * its own producers before the call. There are no host twins. n = 0 returns
- * at once; n < 2^31.
+ * its own producers before the call. There are no host twins (one exception:
+ * mtx_blocks_light_host below, the CPU reference of the two light-path
+ * entries, which the oracle does not cover). n = 0 returns at once; n < 2^31.
  *   Indices that arrive in caller tensors (material, emitter, prim) are
  * compared against the scene's counts on the device before any load that
  * depends on them: one out of range is treated as invalid (null BSDF, no
@@ -652,6 +653,48 @@ int mtx_blocks_math_dev(mtx_ctx *ctx, int op, uint64_t n, const float *a, const 
  * give the rays the formula gives. Masked-off lanes get zeros. */
 int mtx_blocks_sensor_ray_dev(mtx_ctx *ctx, uint64_t n, const float *pos, const uint8_t *active, float *o, float *d,
                               float *maxt);
+/* scene.sample_emitter_ray(time, sample1, u_pos, u_dir) (bdpt02.py:86-88):
+ * the first ray of a light path, from u_pos, u_dir (2, n). u_pos.x picks the
+ * emitter (the environment, if any, is index n_emitters) and is reused;
+ * the position is the emitter's sample_position, the direction a cosine
+ * hemisphere about its normal. o, d (3, n), maxt (n): spawn_ray(p, nrm, d) of
+ * an area emitter, or the unoffset point of the scene's bounding sphere for
+ * the environment. weight (3, n) = radiance * pi / pdf_pos * count (area),
+ * radiance * 4 pi^2 r^2 * count (environment). p, nrm (3, n): the unoffset
+ * position and the normal; emitter (n): the picked index. A scene without
+ * emitters gives zeros and emitter = -1, as a masked-off lane does. */
+int mtx_blocks_sample_emitter_ray_dev(mtx_ctx *ctx, uint64_t n, const float *u_pos, const float *u_dir,
+                                      const uint8_t *active, float *o, float *d, float *maxt, float *weight, float *p,
+                                      float *nrm, int32_t *emitter);
+/* sensor.sample_direction(it, ..) of the context's bound camera: connects the
+ * points p (3, n) to the pinhole. pos (2, n): the film position in pixels;
+ * d (3, n), dist (n): the unit direction from p to the camera origin and the
+ * distance; weight (n) = importance / dist^2 with importance = 1 / (4 tan_x
+ * tan_y cos^3 theta), normalised over the image rectangle; valid (n bytes):
+ * 0 outside the clip range or the frustum, where all outputs are zero.
+ * test_visibility != 0 traces spawn_ray_to(p, nrm, origin) (nrm (3, n): the
+ * geometric normal at p, read only then) through the any-hit tree in the same
+ * launch and zeroes the weight of an occluded sample; valid is unchanged. */
+int mtx_blocks_sensor_direction_dev(mtx_ctx *ctx, uint64_t n, const float *p, const float *nrm,
+                                    const uint8_t *active, int test_visibility, float *pos, float *d, float *dist,
+                                    float *weight, uint8_t *valid);
+/* Host-only, needs no context (like mtx_bvh_build): the per-lane functions of
+ * the two entries above, run on the CPU over a host scene description. The
+ * one exception to "there are no host twins": the library's host code is
+ * compiled with the kernels' floating-point flags, so these are the kernels'
+ * bit-exact twins, and the reference the tests hold them to. in / out are
+ * host (C, n) planes; integers are stored as bit patterns.
+ *   MTX_LIGHT_EMITTER_RAY       in (4, n) = u_pos, u_dir; out (17, n) = o, d,
+ *     maxt, weight, p, nrm, emitter (int32). Needs the emitters, the vertex
+ *     and index arrays, shapes and tables of the description; no BVH.
+ *   MTX_LIGHT_SENSOR_DIRECTION  in (3, n) = p; out (8, n) = pos, d, dist,
+ *     weight, valid (uint32 0 / 1), without the visibility test. Reads
+ *     desc->camera alone.
+ *   MTX_LIGHT_PROJECT           in (3, n) = p; out (3, n) = the film position
+ *     of the projection sample_direction shares with ReSTIR's reprojection
+ *     (mtx_core/restir.h project_prev) and its validity (uint32 0 / 1). */
+enum { MTX_LIGHT_EMITTER_RAY = 0, MTX_LIGHT_SENSOR_DIRECTION = 1, MTX_LIGHT_PROJECT = 2 };
+int mtx_blocks_light_host(const mtx_scene_desc *desc, int op, uint64_t n, const float *in, float *out);
 /* ImageBlock.put (path.py:101): stage 1 of the film (DESIGN.md "Film") for
  * samples the caller holds. The film is the caller's: `planes` are the
  * contribution planes of the band of rows [y0, y1) of a film `width` wide,

@@ -6,12 +6,15 @@
 //   Scene::sample_emitter_direction / pdf_emitter_direction,
 //   AreaEmitter + Rectangle, AreaEmitter + Mesh (Mesh::sample_position),
 //   ConstantBackgroundEmitter (`constant`),
-//   PerspectiveCamera::sample_ray.
+//   PerspectiveCamera::sample_ray / sample_direction,
+//   Scene::sample_emitter_ray over AreaEmitter:: and
+//   ConstantBackgroundEmitter::sample_ray (the light-path side).
 #pragma once
 #include "../mtx.h"
 #include "bsdf.h"
 #include "common.h"
 #include "discrete.h"
+#include "restir.h"
 #include "warp.h"
 
 namespace mtx {
@@ -328,6 +331,66 @@ MTX_HD V3 sample_emitter_direction(const SceneView &s, V3 ref_p, V2 u, Direction
   return spec;
 }
 
+// Scene::sample_emitter_ray(time, sample1, sample2 = u_pos, sample3 = u_dir)
+// over AreaEmitter::sample_ray: the start of a light path. The emitter is
+// picked from u_pos.x with the reuse and the index arithmetic of
+// sample_emitter_direction; the position is Rectangle:: / Mesh::sample_position
+// (pdf_pos = inv_area), the direction square_to_cosine_hemisphere(u_dir) about
+// the emitter normal, the ray leaves through spawn_ray(p, n, d), and
+//   weight = radiance * pi / pdf_pos * count
+// (emitted radiance * cos / (pdf_pos * cos / pi), times the pick's 1 / pdf).
+// The environment (ConstantBackgroundEmitter::sample_ray) starts on the
+// scene's bounding sphere, origin = centre + square_to_uniform_sphere(u_pos) *
+// radius (no offset: the sphere already clears the scene), aims a cosine
+// hemisphere about the inward normal, and carries radiance * 4 pi^2 r^2 * count.
+// `p`, `n` are the unoffset position and the normal the direction was drawn
+// about. Without emitters: zeros and emitter = -1.
+struct EmitterRaySample {
+  Ray ray;
+  V3 weight, p, n;
+  int32_t emitter;
+};
+MTX_HD void sample_emitter_ray(const SceneView &s, V2 u_pos, V2 u_dir, EmitterRaySample *out) {
+  out->ray = Ray{v3s(0.f), v3s(0.f), 0.f};
+  out->weight = out->p = out->n = v3s(0.f);
+  out->emitter = -1;
+  const uint32_t count = emitter_count(s);
+  if (count == 0) return;
+  const float count_f = (float)count;
+  float scaled = u_pos.x * count_f;
+  uint32_t index = (uint32_t)scaled;
+  if (index > count - 1u) index = count - 1u;
+  u_pos.x = scaled - (float)index;
+  out->emitter = (int32_t)index;
+  const V3 local = square_to_cosine_hemisphere(u_dir);
+  if ((int32_t)index == env_index(s)) {
+    const V3 v0 = square_to_uniform_sphere(u_pos);
+    const V3 ctr = V3{s.env_center[0], s.env_center[1], s.env_center[2]};
+    out->p = fma3(v0, s.env_radius, ctr);
+    out->n = -v0;
+    out->ray = Ray{out->p, to_world(frame_from_normal(out->n), local), kLargest};
+    const float area_pi = 4.f * sqr(kPi) * sqr(s.env_radius);
+    out->weight = V3{s.env_radiance[0], s.env_radiance[1], s.env_radiance[2]} * area_pi * count_f;
+    return;
+  }
+  const mtx_emitter e = s.emitters[index];
+  V3 p, n;
+  if (emitter_is_mesh(e)) {
+    mesh_emitter_sample_position(s, e, u_pos, &p, &n);
+  } else {
+    // Rectangle::sample_position, as in sample_emitter_direction
+    float lx = fmaf(u_pos.x, 2.f, -1.f), ly = fmaf(u_pos.y, 2.f, -1.f);
+    V3 c0 = V3{e.col0[0], e.col0[1], e.col0[2]}, c1 = V3{e.col1[0], e.col1[1], e.col1[2]};
+    V3 ctr = V3{e.center[0], e.center[1], e.center[2]};
+    p = fma3(c0, lx, fma3(c1, ly, ctr));
+    n = V3{e.normal[0], e.normal[1], e.normal[2]};
+  }
+  out->p = p;
+  out->n = n;
+  out->ray = spawn_ray(p, n, to_world(frame_from_normal(n), local));
+  out->weight = V3{e.radiance[0], e.radiance[1], e.radiance[2]} * kPi / e.inv_area * count_f;
+}
+
 // Scene::pdf_emitter_direction(ref, ds) for ds = DirectionSample3f(scene, si, ref):
 // shape pdf_position * dist^2 / |cos|, zero unless the emitter faces ref.
 MTX_HD float pdf_emitter_direction(const SceneView &s, int32_t emitter, V3 ds_d, float ds_dist, V3 ds_n) {
@@ -367,6 +430,36 @@ MTX_HD Ray camera_ray(const mtx_camera &c, V2 pos) {
   V3 o = V3{c.origin[0], c.origin[1], c.origin[2]};
   o = fma3(d, near_t, o);
   return Ray{o, d, far_t - near_t};
+}
+
+// PerspectiveCamera::sample_direction: connect the world point p to the
+// pinhole. The film position (pixels) is project_prev's (mtx_core/restir.h),
+// so the projection, the clip test and the frustum test exist once. d points
+// from p to the camera origin; the weight is the importance over the squared
+// distance, importance = 1 / (A cos^3 theta) with A = 4 tan_x tan_y the area
+// of the image rectangle on the plane z = 1 of the camera frame and cos theta
+// the local z of -d. Outside the clip range or the frustum: invalid, zeros.
+struct SensorDirectionSample {
+  V2 pos;
+  V3 d;
+  float dist, weight;
+  bool valid;
+};
+MTX_HD void camera_sample_direction(const mtx_camera &c, V3 p, SensorDirectionSample *out) {
+  out->pos = V2{0.f, 0.f};
+  out->d = v3s(0.f);
+  out->dist = out->weight = 0.f;
+  out->valid = project_prev(c, p, &out->pos.x, &out->pos.y);
+  if (!out->valid) {
+    out->pos = V2{0.f, 0.f};
+    return;
+  }
+  const V3 rel = V3{c.origin[0], c.origin[1], c.origin[2]} - p;
+  out->dist = norm(rel);
+  out->d = normalize(rel);
+  const float ct = dot(V3{c.inv_rows[6], c.inv_rows[7], c.inv_rows[8]}, -out->d);
+  const float importance = 1.f / (4.f * c.tan_x * c.tan_y * (ct * ct * ct));
+  out->weight = importance / sqr(out->dist);
 }
 
 // ------------------------------ MIS ----------------------------------------

@@ -3151,6 +3151,123 @@ int mtx_blocks_sensor_ray_dev(mtx_ctx *c, uint64_t n, const float *pos, const ui
   return blk_end(c, fn, nullptr);
 }
 
+int mtx_blocks_sample_emitter_ray_dev(mtx_ctx *c, uint64_t n, const float *u_pos, const float *u_dir,
+                                      const uint8_t *active, float *o, float *d, float *maxt, float *weight, float *p,
+                                      float *nrm, int32_t *emitter) {
+  const char *fn = "mtx_blocks_sample_emitter_ray_dev";
+  int rc = blk_begin(c, fn, n, true, {u_pos, u_dir, o, d, maxt, weight, p, nrm, emitter});
+  if (rc || n == 0) return rc;
+  if ((rc = need_device(c, fn, {u_pos, u_dir, active, o, d, maxt, weight, p, nrm, emitter}))) return rc;
+  mtxd::launch_blk_sample_emitter_ray(c->scene, (uint32_t)n, u_pos, u_dir, active,
+                                      mtxd::EmitterRayPlanes{o, d, maxt, weight, p, nrm, emitter}, c->stream);
+  return blk_end(c, fn, nullptr);
+}
+
+int mtx_blocks_sensor_direction_dev(mtx_ctx *c, uint64_t n, const float *p, const float *nrm, const uint8_t *active,
+                                    int test_visibility, float *pos, float *d, float *dist, float *weight,
+                                    uint8_t *valid) {
+  const char *fn = "mtx_blocks_sensor_direction_dev";
+  int rc = blk_begin(c, fn, n, true, {p, pos, d, dist, weight, valid});
+  if (rc || n == 0) return rc;
+  if (test_visibility && !nrm) {
+    mtx_set_error("%s: null argument", fn);
+    return MTX_E_ARG;
+  }
+  if ((rc = need_device(c, fn, {p, nrm, active, pos, d, dist, weight, valid}))) return rc;
+  mtxd::launch_blk_sensor_direction(c->scene, (uint32_t)n, p, nrm, active, test_visibility != 0,
+                                    mtxd::SensorDirPlanes{pos, d, dist, weight, valid}, c->stream);
+  return blk_end(c, fn, nullptr);
+}
+
+// The host twin of the two kernels above: the same per-lane functions over a
+// host scene description, one item after the other.
+int mtx_blocks_light_host(const mtx_scene_desc *d, int op, uint64_t n, const float *in, float *out) {
+  const char *fn = "mtx_blocks_light_host";
+  if (!d || (n && (!in || !out))) {
+    mtx_set_error("%s: null argument", fn);
+    return MTX_E_ARG;
+  }
+  if (n >= (1ull << 31)) {
+    mtx_set_error("%s: n >= 2^31", fn);
+    return MTX_E_ARG;
+  }
+  const auto in_at = [&](int c, uint64_t i) { return in[(size_t)c * n + i]; };
+  const auto put = [&](int c, uint64_t i, float v) { out[(size_t)c * n + i] = v; };
+  const auto put3 = [&](int c, uint64_t i, mtx::V3 v) {
+    put(c, i, v.x);
+    put(c + 1, i, v.y);
+    put(c + 2, i, v.z);
+  };
+  if (op == MTX_LIGHT_EMITTER_RAY) {
+    if (d->n_emitters && (!d->emitters || !d->vpos || !d->tri_vidx || !d->tri_shape || !d->shapes)) {
+      mtx_set_error("%s: the emitters need the scene's emitter, shape and vertex arrays", fn);
+      return MTX_E_ARG;
+    }
+    if (d->n_emitters)  // no table or triangle index is trusted
+      if (int rc = check_mesh_emitters(d)) return rc;
+    for (uint32_t e = 0; e < d->n_emitters; ++e)
+      if (mtx::emitter_is_mesh(d->emitters[e]))
+        for (uint32_t k = 0; k < d->emitters[e].mesh_count; ++k) {
+          uint32_t prim;
+          memcpy(&prim, d->tables + d->emitters[e].mesh_offset + 2 * (size_t)d->emitters[e].mesh_count + k, 4);
+          for (int j = 0; j < 3; ++j)
+            if (d->tri_vidx[3 * (size_t)prim + j] >= d->n_verts) {
+              mtx_set_error("%s: triangle %u names vertex %u of %u", fn, prim, d->tri_vidx[3 * (size_t)prim + j],
+                            d->n_verts);
+              return MTX_E_ARG;
+            }
+        }
+    mtx::SceneView s{};
+    s.tri_vidx = d->tri_vidx;
+    s.tri_shape = d->tri_shape;
+    s.vpos = d->vpos;
+    s.shapes = d->shapes;
+    s.emitters = d->emitters;
+    s.bsdf.tables = d->tables;
+    s.n_tris = d->n_tris;
+    s.n_emitters = d->n_emitters;
+    s.has_env = d->has_env ? 1u : 0u;
+    for (int k = 0; k < 3; ++k) s.env_radiance[k] = d->env_radiance[k];
+    if (s.has_env) mtx::env_bsphere(d->vpos, d->vpos ? d->n_verts : 0, s.env_center, &s.env_radius);
+    for (uint64_t i = 0; i < n; ++i) {
+      mtx::EmitterRaySample es;
+      mtx::sample_emitter_ray(s, mtx::V2{in_at(0, i), in_at(1, i)}, mtx::V2{in_at(2, i), in_at(3, i)}, &es);
+      put3(0, i, es.ray.o);
+      put3(3, i, es.ray.d);
+      put(6, i, es.ray.maxt);
+      put3(7, i, es.weight);
+      put3(10, i, es.p);
+      put3(13, i, es.n);
+      put(16, i, mtx::u2f((uint32_t)es.emitter));
+    }
+    return MTX_OK;
+  }
+  if (op == MTX_LIGHT_SENSOR_DIRECTION || op == MTX_LIGHT_PROJECT) {
+    for (uint64_t i = 0; i < n; ++i) {
+      const mtx::V3 p = mtx::V3{in_at(0, i), in_at(1, i), in_at(2, i)};
+      if (op == MTX_LIGHT_PROJECT) {
+        float ux = 0.f, uy = 0.f;
+        const bool ok = mtx::project_prev(d->camera, p, &ux, &uy);
+        put(0, i, ok ? ux : 0.f);
+        put(1, i, ok ? uy : 0.f);
+        put(2, i, mtx::u2f(ok ? 1u : 0u));
+        continue;
+      }
+      mtx::SensorDirectionSample sd;
+      mtx::camera_sample_direction(d->camera, p, &sd);
+      put(0, i, sd.pos.x);
+      put(1, i, sd.pos.y);
+      put3(2, i, sd.d);
+      put(5, i, sd.dist);
+      put(6, i, sd.weight);
+      put(7, i, mtx::u2f(sd.valid ? 1u : 0u));
+    }
+    return MTX_OK;
+  }
+  mtx_set_error("%s: unknown op %d", fn, op);
+  return MTX_E_ARG;
+}
+
 }  // extern "C"
 
 // The band and filter of a caller-owned film: checked, never trusted.

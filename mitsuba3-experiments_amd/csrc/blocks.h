@@ -38,6 +38,23 @@ void launch_blk_math(int op, uint32_t n, const float *a, const float *b, const f
 // o, d (3, n) and maxt (n, may be null) of camera_ray(cam, pos / size); masked-off lanes: zeros.
 void launch_blk_sensor_ray(const mtx_camera &cam, uint32_t n, const float *pos, const uint8_t *active, float *o,
                            float *d, float *maxt, hipStream_t st);
+// scene.sample_emitter_ray: the ray o, d (3, n), maxt (n), its weight (3, n),
+// the unoffset position and normal p, nrm (3, n) and the emitter index (n).
+struct EmitterRayPlanes {
+  float *o, *d, *maxt, *weight, *p, *n;
+  int32_t *emitter;
+};
+void launch_blk_sample_emitter_ray(const DevScene &s, uint32_t n, const float *u_pos, const float *u_dir,
+                                   const uint8_t *active, const EmitterRayPlanes &out, hipStream_t st);
+// sensor.sample_direction of s.camera from p (3, n); nrm (3, n) is read only
+// with test_visibility (the connection ray's offset side).
+struct SensorDirPlanes {
+  float *pos, *d, *dist, *weight;
+  uint8_t *valid;
+};
+void launch_blk_sensor_direction(const DevScene &s, uint32_t n, const float *p, const float *nrm,
+                                 const uint8_t *active, int test_visibility, const SensorDirPlanes &out,
+                                 hipStream_t st);
 
 // Film put (mtx_blocks_film_put_dev): the band [y0, y1) of a film `width`
 // wide, its filter, and the contribution planes [slot 8][K][band_px] float4.

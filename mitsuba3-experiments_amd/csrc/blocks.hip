@@ -278,6 +278,63 @@ __global__ __launch_bounds__(kBlkBlock) void k_blk_sensor_ray(mtx_camera cam, ui
   }
 }
 
+// scene.sample_emitter_ray (bdpt02.py:86-88): the start of a light path.
+__global__ __launch_bounds__(kBlkBlock) void k_blk_sample_emitter_ray(DevScene s, uint32_t n, const float *u_pos,
+                                                                      const float *u_dir, const uint8_t *active,
+                                                                      EmitterRayPlanes out) {
+  const SceneView view = make_view(s);
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    EmitterRaySample es;
+    if (lane_on(active, i)) {
+      sample_emitter_ray(view, ld2(u_pos, n, i), ld2(u_dir, n, i), &es);
+    } else {
+      es.ray = Ray{v3s(0.f), v3s(0.f), 0.f};
+      es.weight = es.p = es.n = v3s(0.f);
+      es.emitter = -1;
+    }
+    st3(out.o, n, i, es.ray.o);
+    st3(out.d, n, i, es.ray.d);
+    out.maxt[i] = es.ray.maxt;
+    st3(out.weight, n, i, es.weight);
+    st3(out.p, n, i, es.p);
+    st3(out.n, n, i, es.n);
+    out.emitter[i] = es.emitter;
+  }
+}
+
+// sensor.sample_direction: camera_sample_direction of the bound camera, and
+// with VIS the connection ray spawn_ray_to(p, nrm, origin) through the
+// any-hit tree in the same lane (k_blk_sample_emitter<true>'s shape).
+template <bool VIS>
+__global__ __launch_bounds__(kTraceBlock) void k_blk_sensor_direction(DevScene s, uint32_t n, const float *p,
+                                                                      const float *nrm, const uint8_t *active,
+                                                                      SensorDirPlanes out) {
+  extern __shared__ int4 blk_lds[];
+  const mtx_camera cam = s.camera;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    SensorDirectionSample sd;
+    sd.pos = V2{0.f, 0.f};
+    sd.d = v3s(0.f);
+    sd.dist = sd.weight = 0.f;
+    sd.valid = false;
+    if (lane_on(active, i)) {
+      const V3 ref = ld3(p, n, i);
+      camera_sample_direction(cam, ref, &sd);
+      if (VIS && sd.valid) {
+        const Ray sr = spawn_ray_to(ref, ld3(nrm, n, i), V3{cam.origin[0], cam.origin[1], cam.origin[2]});
+        const TraceRay r = make_trace_ray(sr.o, sr.d, sr.maxt);
+        uint32_t nv = 0, tv = 0;
+        if (traverse_occ(s, reinterpret_cast<uint32_t *>(blk_lds) + threadIdx.x, r, sr.maxt, nv, tv)) sd.weight = 0.f;
+      }
+    }
+    st2(out.pos, n, i, sd.pos);
+    st3(out.d, n, i, sd.d);
+    out.dist[i] = sd.dist;
+    out.weight[i] = sd.weight;
+    out.valid[i] = sd.valid ? 1 : 0;
+  }
+}
+
 // ------------------------------------------------------------------ film --
 // Stage 1 of the film (DESIGN.md "Film") on samples the caller holds. The
 // contribution planes are the fused film's, [slot][K][band_px] float4; a put
@@ -558,6 +615,20 @@ void launch_blk_sensor_ray(const mtx_camera &cam, uint32_t n, const float *pos, 
                            float *d, float *maxt, hipStream_t st) {
   hipLaunchKernelGGL(k_blk_sensor_ray, dim3(blk_grid(n, kBlkBlock)), dim3(kBlkBlock), 0, st, cam, n, pos, active, o, d,
                      maxt);
+}
+void launch_blk_sample_emitter_ray(const DevScene &s, uint32_t n, const float *u_pos, const float *u_dir,
+                                   const uint8_t *active, const EmitterRayPlanes &out, hipStream_t st) {
+  hipLaunchKernelGGL(k_blk_sample_emitter_ray, dim3(blk_grid(n, kBlkBlock)), dim3(kBlkBlock), 0, st, s, n, u_pos,
+                     u_dir, active, out);
+}
+void launch_blk_sensor_direction(const DevScene &s, uint32_t n, const float *p, const float *nrm,
+                                 const uint8_t *active, int test_visibility, const SensorDirPlanes &out,
+                                 hipStream_t st) {
+  const dim3 grid(blk_grid(n, kTraceBlock)), block(kTraceBlock);
+  if (test_visibility)
+    hipLaunchKernelGGL(k_blk_sensor_direction<true>, grid, block, stack_bytes(s), st, s, n, p, nrm, active, out);
+  else
+    hipLaunchKernelGGL(k_blk_sensor_direction<false>, grid, block, 0, st, s, n, p, nrm, active, out);
 }
 void launch_blk_film_keys(const FilmBand &g, uint32_t n, const float *pos, const uint8_t *active, uint32_t *keys,
                           uint32_t *counts, hipStream_t st) {

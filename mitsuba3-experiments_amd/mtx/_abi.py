@@ -323,6 +323,7 @@ class BsdfPlanes(C.Structure):
 MTX_MATH_FMA, MTX_MATH_DIV, MTX_MATH_RCP, MTX_MATH_SQRT, MTX_MATH_DOT3 = 0, 1, 2, 3, 4
 MTX_MATH_NORM3, MTX_MATH_NORMALIZE3, MTX_MATH_TO_LOCAL, MTX_MATH_TO_WORLD = 5, 6, 7, 8
 MTX_MATH_MIS_A, MTX_MATH_MIS_B = 9, 10
+MTX_LIGHT_EMITTER_RAY, MTX_LIGHT_SENSOR_DIRECTION, MTX_LIGHT_PROJECT = 0, 1, 2
 
 # Every symbol include/mtx.h declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -383,6 +384,9 @@ EXPORTS = [
     "mtx_blocks_bsdf_dev",
     "mtx_blocks_math_dev",
     "mtx_blocks_sensor_ray_dev",
+    "mtx_blocks_sample_emitter_ray_dev",
+    "mtx_blocks_sensor_direction_dev",
+    "mtx_blocks_light_host",
     "mtx_blocks_film_put_dev",
     "mtx_blocks_film_gather_dev",
 ]

@@ -28,6 +28,12 @@ caller owns) and :class:`SamplingIntegrator` (the render loop of
 path.py:103-192; ``mtx.register_integrator`` / ``mtx.load_dict`` take a
 subclass) make it a renderer whose raw film equals the fused integrator's
 bit for bit when the loop restates that integrator.
+
+Paths may also start at the lights: ``Scene.sample_emitter_ray`` emits,
+``Sensor.sample_direction`` connects a surface point to the camera,
+:class:`AdjointIntegrator` is the render loop that splats through
+``Film.put``'s general path, and :class:`ParticleTracer` (``"ptracer"``) is
+the estimator built on them.
 """
 from __future__ import annotations
 
@@ -292,6 +298,23 @@ class DirectionSample:
             setattr(self, k, _empty(dev, c, n, torch.int32 if k == "emitter" else None))
 
 
+class EmitterSample:
+    """The start of a light path: p, n (3, N), the unoffset position and the
+    normal the direction was drawn about, and emitter (N, int32), the picked
+    index (the environment: n_emitters; -1: no emitter, or a masked-off lane)."""
+
+    def __init__(self, p, n, emitter):
+        self.p, self.n, self.emitter = p, n, emitter
+
+
+class SensorDirectionSample:
+    """sensor.sample_direction planes: pos (2, N) film position in pixels,
+    d (3, N) unit direction towards the camera, dist, weight (N), valid (N, bool)."""
+
+    def __init__(self, pos, d, dist, weight, valid):
+        self.pos, self.d, self.dist, self.weight, self.valid = pos, d, dist, weight, valid
+
+
 class BSDFSample:
     """BSDFSample3f planes: wo (3, N, local), pdf, eta (N), sampled_type (N, int32 BSDFFlags bits)."""
 
@@ -398,6 +421,27 @@ class Scene:
                                                       u.data_ptr(), am, int(bool(test_visibility)), C.byref(pl),
                                                       w.data_ptr()), "mtx_blocks_sample_emitter_dev")
         return ds, w
+
+    def sample_emitter_ray(self, u_pos, u_dir, active=None):
+        """scene.sample_emitter_ray(time, sample1, u_pos, u_dir, active)
+        (bdpt02.py:86-88) -> (Ray, weight (3, N), EmitterSample). u_pos.x picks
+        the emitter and is reused; the position is the emitter's
+        sample_position, the direction a cosine hemisphere about its normal;
+        weight = radiance * pi / pdf_pos * count (the environment: radiance *
+        4 pi^2 r^2 * count, from the scene's bounding sphere)."""
+        torch = _torch()
+        n = _f32("sample_emitter_ray: u_pos", u_pos, 2, None)
+        dev = u_pos.device
+        _f32("sample_emitter_ray: u_dir", u_dir, 2, n, dev)
+        _, am = _mask("sample_emitter_ray: active", active, n, dev)
+        o, d, maxt, w = _empty(dev, 3, n), _empty(dev, 3, n), _empty(dev, None, n), _empty(dev, 3, n)
+        es = EmitterSample(_empty(dev, 3, n), _empty(dev, 3, n), _empty(dev, None, n, torch.int32))
+        if n:
+            check(lib().mtx_blocks_sample_emitter_ray_dev(self._call(dev), n, u_pos.data_ptr(), u_dir.data_ptr(), am,
+                                                          o.data_ptr(), d.data_ptr(), maxt.data_ptr(), w.data_ptr(),
+                                                          es.p.data_ptr(), es.n.data_ptr(), es.emitter.data_ptr()),
+                  "mtx_blocks_sample_emitter_ray_dev")
+        return Ray(o, d, maxt), w, es
 
     def _emitter(self, name, emitter, d, dist, nrm, wi, active, want_pdf, want_le):
         n = _i32(f"{name}: emitter", emitter, None)
@@ -535,6 +579,52 @@ class Sensor:
             check(lib().mtx_blocks_sensor_ray_dev(self.ctx.handle, n, pos.data_ptr(), am, o.data_ptr(), d.data_ptr(),
                                                   maxt.data_ptr()), "mtx_blocks_sensor_ray_dev")
         return Ray(o, d, maxt)
+
+    def sample_direction(self, p, n, test_visibility: bool = True, active=None) -> SensorDirectionSample:
+        """sensor.sample_direction(it, ..): connect the points p (3, N), whose
+        geometric normals are n (3, N), to the pinhole. ``weight`` is the
+        importance over the squared distance, importance = 1 / (4 tan_x tan_y
+        cos^3 theta); outside the clip range or the frustum a lane is not
+        ``valid`` and all its outputs are zero. With test_visibility the
+        connection ray spawn_ray_to(p, n, origin) runs through the any-hit
+        tree in the same launch and an occluded sample's weight is zero."""
+        torch = _torch()
+        cnt = _f32("sample_direction: p", p, 3, None)
+        dev = p.device
+        _f32("sample_direction: n", n, 3, cnt, dev)
+        _, am = _mask("sample_direction: active", active, cnt, dev)
+        pos, d, dist, w = _empty(dev, 2, cnt), _empty(dev, 3, cnt), _empty(dev, None, cnt), _empty(dev, None, cnt)
+        valid = _empty(dev, None, cnt, torch.uint8)
+        if cnt:
+            idx = dev.index if dev.index is not None else torch.cuda.current_device()
+            if idx != self.ctx.device:
+                raise MtxError(f"tensors on cuda:{idx}, the sensor is bound to cuda:{self.ctx.device}")
+            torch.cuda.current_stream(dev).synchronize()  # libmtx runs on its own stream
+            self._bind(self.ctx, self.scene)
+            check(lib().mtx_blocks_sensor_direction_dev(self.ctx.handle, cnt, p.data_ptr(), n.data_ptr(), am,
+                                                        int(bool(test_visibility)), pos.data_ptr(), d.data_ptr(),
+                                                        dist.data_ptr(), w.data_ptr(), valid.data_ptr()),
+                  "mtx_blocks_sensor_direction_dev")
+        return SensorDirectionSample(pos, d, dist, w, valid.bool())
+
+
+def light_host(scene, op: int, values) -> np.ndarray:
+    """The CPU twin of the two light-path kernels (mtx_blocks_light_host,
+    include/mtx.h): needs no GPU. ``scene``: an ``mtx.scene.Scene``; ``op``:
+    ``_abi.MTX_LIGHT_*``; ``values``: the (C, N) float32 input planes. Returns
+    the (C', N) float32 output planes, integer outputs as bit patterns."""
+    rows = {_abi.MTX_LIGHT_EMITTER_RAY: (4, 17), _abi.MTX_LIGHT_SENSOR_DIRECTION: (3, 8),
+            _abi.MTX_LIGHT_PROJECT: (3, 3)}
+    if op not in rows:
+        raise MtxError(f"light_host: unknown op {op!r}")
+    a = np.ascontiguousarray(values, np.float32)
+    if a.ndim != 2 or a.shape[0] != rows[op][0]:
+        raise MtxError(f"light_host: input of shape {a.shape}, expected ({rows[op][0]}, N)")
+    out = np.zeros((rows[op][1], a.shape[1]), np.float32)
+    desc = _mtx_scene(scene).desc()
+    check(lib().mtx_blocks_light_host(C.byref(desc), int(op), a.shape[1], a.ctypes.data, out.ctypes.data),
+          "mtx_blocks_light_host")
+    return out
 
 
 # -------------------------------------------------------------------- film --
@@ -706,3 +796,230 @@ class SamplingIntegrator:
         if not develop:
             return raw
         return globals()["develop"](raw, _abi.RFILTER_BORDER[self.rfilter_id(scene, rfilter)])
+
+
+# ----------------------------------------------------- adjoint integrators --
+
+class AdjointIntegrator:
+    """Base class of an integrator that starts its paths at the lights and
+    splats onto the film (Mitsuba's ``AdjointIntegrator``). Override
+    :meth:`sample`, which emits ``sampler.n`` particles and adds their
+    contributions with :meth:`splat`.
+
+    :meth:`render_film` traces ``spp * width * height`` particles in passes
+    of at most ``samples_per_pass`` (property, default 2^20), each with a
+    :class:`Sampler` seeded by the global particle indices of the pass, so the
+    film depends on the seed and the particle count alone: the same seed and
+    count give the same bits. Contributions are scaled by ``sample_scale =
+    pixel_count / total_particles``. The raw film it returns has the layout
+    of :meth:`SamplingIntegrator.render_film`, with the weight channel set to
+    1 (the sum of the splats is the estimate; Mitsuba overwrites the channel
+    the same way), so ``develop`` applies unchanged.
+
+    Filters: "box" (the default here) and "tent", whose taps sum to 1. With
+    the tent the outermost pixels miss the share of splats that would arrive
+    from positions outside the frustum. "gaussian" is refused: its taps do
+    not sum to 1."""
+
+    name = ""
+
+    def __init__(self, props=None):
+        from .integrators import Properties
+
+        self.props = Properties(props or {})
+        self.rfilter = self.props.get("rfilter", "box")
+        self.samples_per_pass = int(self.props.get("samples_per_pass", 1 << 20))
+        if self.samples_per_pass <= 0:
+            raise MtxError(f"samples_per_pass = {self.samples_per_pass}: expected a positive particle count")
+
+    def rfilter_id(self, scene, rfilter=None) -> int:
+        from .integrators import SamplingIntegrator as Fixed
+
+        fid = Fixed.rfilter_id(self, _mtx_scene(scene), rfilter)
+        if fid == _abi.RFILTERS["gaussian"]:
+            raise MtxError("an adjoint integrator splats unnormalised contributions: the gaussian filter's taps do "
+                           "not sum to 1; use 'box' or 'tent'")
+        return fid
+
+    def check_scene(self, scene) -> None:
+        """Refuse a scene the estimator cannot render (MtxError); the default accepts all."""
+
+    def sample(self, scene, sensor, sampler, film, sample_scale) -> None:
+        """Emit sampler.n particles into `film`. scene: :class:`Scene`,
+        sensor: :class:`Sensor`, sampler: :class:`Sampler` (untouched),
+        sample_scale: the factor every contribution carries."""
+        raise NotImplementedError(f"{type(self).__name__} does not override sample()")
+
+    def splat(self, film, pos, value, active) -> None:
+        """``Film.put`` of the contributions value (3, N) at the film
+        positions pos (2, N) through the general path. Lanes that are off, or
+        whose position lies on the film's upper edge or outside the band, are
+        masked, so the put drops nothing."""
+        on = active & (pos[0] >= 0) & (pos[0] < film.width) & (pos[1] >= film.y0) & (pos[1] < film.y1)
+        dropped = film.put(pos, value.contiguous(), active=on)
+        if dropped:
+            raise MtxError(f"splat: {dropped} contributions with a non-finite film position")
+
+    def render_film(self, scene, seed: int = 0, spp: int = 1, y0: int = 0, y1: int | None = None, sensor=None,
+                    rfilter=None, samples_per_pass: int | None = None):
+        """The raw film tensor of rows [y0, y1): (rows + 2b, W + 2b, 4), RGB =
+        the scaled sum of the splats, weight = 1. The particles are those of
+        the whole film whatever the band."""
+        torch = _torch()
+        fid = self.rfilter_id(scene, rfilter)
+        sens = Sensor(scene, sensor)
+        scn = Scene(sens.scene, sens.ctx.device)
+        self.check_scene(scn)
+        W, H = sens.width, sens.height
+        y0, y1 = int(y0), int(H if y1 is None else y1)
+        spp = int(spp)
+        per_pass = int(self.samples_per_pass if samples_per_pass is None else samples_per_pass)
+        total = spp * W * H
+        if spp <= 0 or not 0 <= y0 < y1 <= H or per_pass <= 0 or total >= 2 ** 32:
+            raise MtxError("render_film: bad rows / spp / samples_per_pass arguments (spp * W * H < 2^32)")
+        film = Film(W, y0, y1, fid, sens.ctx.device)
+        dev = film.device
+        scale = float(np.float32(W * H) / np.float32(total))
+        for i0 in range(0, total, per_pass):
+            lanes = torch.arange(i0, min(total, i0 + per_pass), dtype=torch.int64, device=dev)
+            lanes = torch.where(lanes >= 2 ** 31, lanes - 2 ** 32, lanes).to(torch.int32)  # uint32 bit patterns
+            self.sample(scn, sens, Sampler(seed, lanes), film, scale)
+        raw = film.raw()
+        raw[..., 3] = 1.0
+        return raw
+
+    def render(self, scene, sensor=None, seed: int = 0, spp: int = 1, develop: bool = True, rfilter=None,
+               samples_per_pass: int | None = None):
+        """The (H, W, 3) image tensor, or the raw film with develop=False."""
+        raw = self.render_film(scene, seed=seed, spp=spp, sensor=sensor, rfilter=rfilter,
+                               samples_per_pass=samples_per_pass)
+        if not develop:
+            return raw
+        return globals()["develop"](raw, _abi.RFILTER_BORDER[self.rfilter_id(scene, rfilter)])
+
+
+class _Point:
+    """The p, n planes a block reads from an interaction."""
+
+    def __init__(self, p, n):
+        self.p, self.n = p, n
+
+
+class ParticleTracer(AdjointIntegrator):
+    """Mitsuba's ``ptracer`` on the blocks: particles leave the emitters, and
+    every vertex of a light path is connected to the pinhole.
+
+    Properties (defaults are Mitsuba's): ``max_depth`` (-1 = unbounded; counts
+    segments as path_test does: 1 renders the directly visible emitters only,
+    2 adds emitter - surface - camera, ...), ``rr_depth`` (5: Russian roulette
+    starts once a light path has that many segments), ``hide_emitters``
+    (False), ``samples_per_pass`` (2^20 here; Mitsuba's default is one pass).
+
+    Phase 1, directly visible emitters: the light path's own starting point
+    (``EmitterSample``) is connected to the sensor and carries Le cos =
+    weight / pi * cos. For the environment the point is instead sampled as a
+    direction from the camera (``sample_emitter_direction`` at the camera
+    origin), as Mitsuba does for infinite emitters: the bounding sphere need
+    not contain the camera.
+
+    Phase 2, per bounce: ``ray_intersect``; the sensor connection with its
+    shadow ray; ``bsdf_eval_pdf_sample`` for the value towards the camera and
+    for the continuation; the shading-normal correction of the adjoint BSDF
+    (Veach, p. 155), |wi.n_s wo.n_g| / |wo.n_s wi.n_g| with wi towards the
+    previous vertex, and no transport where a direction lies on different
+    sides of the two normals; Russian roulette on the throughput relative to
+    the emitted weight; ``spawn_ray``. The BSDF block evaluates in radiance
+    mode: the only asymmetric material it can connect through is the smooth
+    dielectric, whose transmitted sample carries eta_ti^2, undone here from
+    ``sampled_type`` and ``eta``. A ``roughdielectric`` is refused."""
+
+    name = "ptracer"
+
+    def __init__(self, props=None):
+        super().__init__(props)
+        self.max_depth = int(self.props.get("max_depth", -1))
+        self.rr_depth = int(self.props.get("rr_depth", 5))
+        self.hide_emitters = bool(self.props.get("hide_emitters", False))
+        if self.max_depth < -1:
+            raise MtxError(f"max_depth = {self.max_depth}: expected -1 (unbounded) or a segment count >= 0")
+
+    def check_scene(self, scene) -> None:
+        for i, m in enumerate(scene.scene.materials):
+            if m.type == _abi.MTX_MAT_ROUGHDIELECTRIC:
+                raise MtxError(f"ptracer: material {i} is a roughdielectric: connecting a light path through it needs "
+                               "the adjoint of its BSDF (its eta), which the blocks evaluate in radiance mode only")
+
+    @staticmethod
+    def _adjoint(si, wi_g, wo_local, wo_world):
+        """(mask, correction) of the adjoint BSDF for the outgoing direction."""
+        torch = _torch()
+        wo_g = dot(si.n, wo_world)
+        cwi, cwo = si.wi[2], wo_local[2]
+        ok = (wi_g * cwi > 0) & (wo_g * cwo > 0)
+        den = cwo * wi_g
+        corr = torch.abs(div(cwi * wo_g, torch.where(ok, den, torch.ones_like(den))))
+        return ok, corr
+
+    def sample(self, scene, sensor, sampler, film, sample_scale) -> None:
+        torch = _torch()
+        n, dev = sampler.n, sampler.device
+        max_depth = 2 ** 31 - 1 if self.max_depth < 0 else self.max_depth
+        if n == 0 or max_depth == 0:
+            return
+        ray, weight, es = scene.sample_emitter_ray(sampler.next_2d(), sampler.next_2d())
+        alive = es.emitter >= 0
+        if not self.hide_emitters:
+            p, nrm = es.p, es.n
+            le = weight * float(np.float32(1.0 / np.pi))
+            env = None
+            if scene.has_environment:
+                # the sky seen directly: a direction from the camera, pdf 1 / (4 pi), target two radii away
+                env = es.emitter == len(scene.scene.emitters)
+                cam = torch.tensor(list(sensor.scene.camera.origin), dtype=torch.float32, device=dev)
+                ref = _Point(cam[:, None].expand(3, n).contiguous(), torch.zeros((3, n), device=dev))
+                count = len(scene.scene.emitters) + 1
+                u = sampler.next_2d()
+                u = torch.stack([(u[0] + float(count - 1)) / float(count), u[1]])  # the pick: the sky
+                ds, le_env = scene.sample_emitter_direction(ref, u, False, env)
+                p, nrm = torch.where(env, ds.p, p), torch.where(env, ds.n, nrm)
+            sd = sensor.sample_direction(p, nrm, True, alive)
+            cos_l = dot(nrm, sd.d)
+            geom = cos_l
+            if env is not None:
+                geom = torch.where(env, sd.dist * sd.dist, cos_l)
+                le = torch.where(env, le_env, le)
+            on = alive & sd.valid & (cos_l > 0)
+            self.splat(film, sd.pos, le * (geom * sd.weight * float(sample_scale)), on)
+        # the light paths: k segments so far; a connection makes it k + 1
+        throughput, rel = weight, torch.ones((3, n), device=dev)
+        eta = torch.ones(n, device=dev)
+        o, d, maxt = ray.o, ray.d, ray.maxt
+        k = 1
+        while k + 1 <= max_depth and bool(alive.any()):
+            si = scene.ray_intersect(o, d, maxt, alive)
+            alive = alive & si.valid
+            wi_g = dot(si.n, si.to_world(si.wi))
+            sd = sensor.sample_direction(si.p, si.n, True, alive)
+            wo = si.to_local(sd.d)
+            s1, s2 = sampler.next_1d(), sampler.next_2d()
+            val, _pdf, bs, bw = scene.bsdf_eval_pdf_sample(si, wo, s1, s2, alive)
+            ok, corr = self._adjoint(si, wi_g, wo, sd.d)
+            self.splat(film, sd.pos, throughput * val * (corr * sd.weight * float(sample_scale)),
+                       alive & sd.valid & ok)
+            k += 1
+            if k + 1 > max_depth:
+                break
+            wo_w = si.to_world(bs.wo)
+            ok, corr = self._adjoint(si, wi_g, bs.wo, wo_w)
+            transmitted = (bs.sampled_type & 0x40) != 0  # BF_DELTA_TRANSMISSION: undo the radiance scale eta_ti^2
+            bw = torch.where(transmitted, bw * (bs.eta * bs.eta), bw) * corr
+            throughput, rel = throughput * bw, rel * bw
+            eta = eta * bs.eta
+            fmax = torch.fmax(torch.fmax(rel[0], rel[1]), rel[2])
+            alive = alive & ok & (fmax > 0)
+            if k >= self.rr_depth:
+                q = torch.fmin(fmax * (eta * eta), fmax.new_tensor(0.95))
+                alive = alive & (sampler.next_1d() < q)
+                inv_q = rcp(torch.where(alive, q, torch.ones_like(q)))
+                throughput, rel = throughput * inv_q, rel * inv_q
+            o, d, maxt = si.spawn_ray(wo_w)

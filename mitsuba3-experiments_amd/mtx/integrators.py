@@ -543,6 +543,15 @@ register_integrator("integrator", lambda props: Simple(props))  # simple.py:119
 register_integrator("nerad", lambda props: NeradIntegrator(props))
 
 
+def _register_blocks_integrators() -> None:
+    from .blocks import ParticleTracer
+
+    register_integrator("ptracer", ParticleTracer)  # testpssmlt.py:22-27; written on mtx.blocks
+
+
+_register_blocks_integrators()
+
+
 def scene_with_sensor(scene, sensor):
     """The scene seen through `sensor` -- the ``sensor`` argument of
     SamplingIntegrator.render / mi.render (testpssmlt.py:45, pssmlt.py:167-175,
@@ -731,10 +740,10 @@ def register_with_mitsuba(mi=None) -> bool:
         except Exception:
             return False
     _wrap_loaders(mi)
-    from .blocks import SamplingIntegrator as BlocksIntegrator
+    from .blocks import AdjointIntegrator, SamplingIntegrator as BlocksIntegrator
 
     for name, ctor in list(_REGISTRY.items()):
-        if isinstance(ctor, type) and issubclass(ctor, BlocksIntegrator):
+        if isinstance(ctor, type) and issubclass(ctor, (BlocksIntegrator, AdjointIntegrator)):
             continue  # integrators written on mtx.blocks work on torch tensors: mtx.load_dict only
         mi.register_integrator(name, _mitsuba_plugin(mi, name, ctor))
     return True

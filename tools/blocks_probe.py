@@ -19,7 +19,15 @@ general path and ``Film.raw`` at N lanes beside torch's ``copy_`` of the same
 contribution planes, and a whole ``render_film`` composed on the blocks
 against the fused integrator's on the same frame.
 
-Usage: python tools/blocks_probe.py [--only blocks|film] [--log2n 22] [--reps 5] [--scenes small,full] [--out FILE]
+With ``--only light`` (profiles/blocks_light_probe.json): the two light-path
+calls, ``scene.sample_emitter_ray`` and ``sensor.sample_direction`` with and
+without its visibility test, at N lanes beside torch's ``copy_`` of the same
+planes, and a whole ``ptracer`` frame beside the composed ``path_test`` frame
+of the same film and sample count. The frame's scene is the Cornell box of
+tests/blocks_light_cases.py: the bedroom proxy holds a roughdielectric, which
+the particle tracer refuses.
+
+Usage: python tools/blocks_probe.py [--only blocks|film|light] [--log2n 22] [--reps 5] [--scenes small,full] [--out FILE]
 """
 import argparse
 import json
@@ -188,29 +196,81 @@ def probe_film(label, sc, n, reps):
                             "films_bit_identical": same}}
 
 
+def probe_light(label, sc, n, reps):
+    """The two light-path calls at n lanes on `sc`, and a ptracer frame beside
+    the composed path_test frame on the Cornell box."""
+    import blocks_integrators as bi
+    import torch
+    from mtx import blocks, load_dict
+    from mtx.mitsuba_dict import scene_from_dict
+    from blocks_light_cases import cornell_dict
+
+    scn, sens = blocks.Scene(sc), blocks.Sensor(sc)
+    g = torch.Generator(device="cuda").manual_seed(7)
+    u_pos, u_dir = torch.rand((2, n), device="cuda", generator=g), torch.rand((2, n), device="cuda", generator=g)
+    ray, _, _ = scn.sample_emitter_ray(u_pos, u_dir)
+    si = scn.ray_intersect(ray.o, ray.d, ray.maxt)  # first vertices of light paths: the points a connection starts at
+    planes17, other17 = torch.empty((17, n), device="cuda"), torch.empty((17, n), device="cuda")
+    planes7, other7 = torch.empty((7, n), device="cuda"), torch.empty((7, n), device="cuda")
+    rows = [
+        row("torch copy_ of 17 planes", timed(lambda: other17.copy_(planes17), reps), n, 136),
+        row("scene.sample_emitter_ray", timed(lambda: scn.sample_emitter_ray(u_pos, u_dir), reps), n, 16 + 68),
+        row("torch copy_ of 7 planes", timed(lambda: other7.copy_(planes7), reps), n, 56),
+        row("sensor.sample_direction (no visibility)", timed(lambda: sens.sample_direction(si.p, si.n, False), reps),
+            n, 12 + 29),
+        row("sensor.sample_direction (visibility)", timed(lambda: sens.sample_direction(si.p, si.n, True), reps), n,
+            24 + 29),
+    ]
+    side = 1 << ((n // FILM_SPP).bit_length() - 1) // 2
+    box = scene_from_dict(cornell_dict(side, side))
+
+    class PathMis(blocks.SamplingIntegrator):
+        def sample(self, scene, sampler, ray, medium=None, active=None):
+            Lr, valid = bi.path_mis(scene, sampler, ray.o, ray.d, 8, 2)
+            return Lr, valid, []
+
+    k = max(3, reps // 2)
+    pt = load_dict({"type": "ptracer", "max_depth": 8, "rr_depth": 2})
+    ptracer = timed(lambda: pt.render_film(box, seed=1, spp=FILM_SPP), k, 1)
+    comp = timed(lambda: PathMis().render_film(box, seed=1, spp=FILM_SPP, rfilter="box"), k, 1)
+    fused_i = load_dict({"type": "path_test", "max_depth": 8, "rr_depth": 2})
+    fused = timed(lambda: fused_i.render_film(box, seed=1, spp=FILM_SPP, rfilter="box"), k, 1)
+    paths = side * side * FILM_SPP
+    mp = lambda t: round(paths / (t["median_ms"] * 1e-3) / 1e6, 2)  # noqa: E731
+    return {"scene": label, "n_tris": int(sc.n_tris), "lanes": n, "blocks": rows,
+            "frame": {"scene": "cornell_box", "film": [side, side], "spp": FILM_SPP, "max_depth": 8, "rr_depth": 2,
+                      "ptracer": {**ptracer, "Mpaths_per_s": mp(ptracer)},
+                      "path_test_composed_on_blocks": {**comp, "Mpaths_per_s": mp(comp)},
+                      "path_test_fused": {**fused, "Mpaths_per_s": mp(fused)},
+                      "ptracer_over_composed": round(ptracer["median_ms"] / comp["median_ms"], 2)}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2n", type=int, default=22)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--scenes", default="small,full")
-    ap.add_argument("--only", default="blocks", choices=["blocks", "film"],
+    ap.add_argument("--only", default="blocks", choices=["blocks", "film", "light"],
                     help="blocks: the per-block rows and the composed sample(); film: sensor rays, Film.put / raw "
-                         "and the composed render_film (default --out: profiles/blocks_film_probe.json)")
+                         "and the composed render_film (default --out: profiles/blocks_film_probe.json); light: "
+                         "sample_emitter_ray, sample_direction and a ptracer frame (profiles/blocks_light_probe.json)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "blocks_probe.json" if a.only == "blocks" else "blocks_film_probe.json")
+        a.out = os.path.join(ROOT, "profiles", {"blocks": "blocks_probe.json", "film": "blocks_film_probe.json",
+                                                "light": "blocks_light_probe.json"}[a.only])
     import torch
     from mtx import scene
 
     if not torch.cuda.is_available():
         raise SystemExit("blocks_probe: needs a GPU (no time is reported from a CPU)")
-    doc = {"probe": a.only if a.only == "blocks" else "blocks film", "hbm_peak_GBps": HBM_PEAK_GBS,
+    doc = {"probe": {"blocks": "blocks", "film": "blocks film", "light": "blocks light"}[a.only], "hbm_peak_GBps": HBM_PEAK_GBS,
            "timing": "host clock around calls that end in a device "
            "synchronise; medians of --reps calls after warm-up", "scenes": []}
     for label in a.scenes.split(","):
         sc = scene.bedroom(width=64, height=36, scale=0.02, tex_res=64) if label == "small" else scene.bedroom()
-        doc["scenes"].append((probe_scene if a.only == "blocks" else probe_film)(label, sc, 1 << a.log2n, a.reps))
+        probe = {"blocks": probe_scene, "film": probe_film, "light": probe_light}[a.only]
+        doc["scenes"].append(probe(label, sc, 1 << a.log2n, a.reps))
         with open(a.out, "w") as f:  # after each scene: a later failure keeps what was measured
             json.dump(doc, f, indent=1)
             f.write("\n")
