@@ -695,6 +695,47 @@ int mtx_blocks_sensor_direction_dev(mtx_ctx *ctx, uint64_t n, const float *p, co
  *     (mtx_core/restir.h project_prev) and its validity (uint32 0 / 1). */
 enum { MTX_LIGHT_EMITTER_RAY = 0, MTX_LIGHT_SENSOR_DIRECTION = 1, MTX_LIGHT_PROJECT = 2 };
 int mtx_blocks_light_host(const mtx_scene_desc *desc, int op, uint64_t n, const float *in, float *out);
+/* A vertex store: one subpath per lane, D = `depth` vertex slots, every plane
+ * coalesced over lanes (vertex k, component c of lane i at [(k * C + c) * n + i]).
+ * mtx_core/bdpt.h states what a camera and a light subpath keep in it. */
+typedef struct mtx_path_planes {
+  uint32_t depth;                      /* D = max vertices per subpath */
+  const int32_t *len;                  /* (n)        vertices recorded for this lane, 0..D */
+  const float *p, *n, *sh_n, *wi;      /* (D, 3, n)  position, geometric / shading normal, wi (local) */
+  const float *uv;                     /* (D, 2, n) */
+  const int32_t *material, *emitter;   /* (D, n)     -1 = none */
+  const float *beta;                   /* (D, 3, n)  throughput with which the subpath arrives at the vertex */
+  const float *pdf_fwd, *pdf_rev;      /* (D, n)     area-measure densities */
+  const uint8_t *delta;                /* (D, n)     the lobe sampled AT this vertex was a delta / null lobe */
+} mtx_path_planes;
+/* Connect a camera subpath z_0 .. and a light subpath y_0 .. per lane
+ * (mtx_core/bdpt.h has the conventions): strategy (s, t) joins y_{s-1} and
+ * z_{t-1}, t >= 2; s = 0 is the camera subpath's own emitter hit. s = t = -1
+ * sums every strategy with s + t - 1 <= max_depth into L (3, n); s, t >= 0
+ * evaluates that one, and `weight` (n, may be NULL; refused with s = t = -1)
+ * receives its weight. flags: MTX_BDPT_MIS weighs the strategies by the power
+ * heuristic (exponent 2) over all strategies of the same path with t' >= 2,
+ * else every weight is 1; MTX_BDPT_VISIBILITY traces the connection's shadow
+ * ray spawn_ray_to(z.p, z.n, y.p) through the any-hit tree in the same lane,
+ * only where the unoccluded contribution is non-zero. A strategy a lane's
+ * subpaths are too short for, or one that touches a vertex without a smooth
+ * lobe, gives 0 (and weight 0). Both stores have the same depth D, max_depth
+ * >= 1, s <= D, 2 <= t <= D. A material or emitter index outside the scene's
+ * tables is handled as none and reported (MTX_E_ARG) like the other blocks'.
+ * Environment emitters are not connected (s = 0 at a miss gives 0). */
+enum { MTX_BDPT_MIS = 1, MTX_BDPT_VISIBILITY = 2 };
+int mtx_blocks_bdpt_connect_dev(mtx_ctx *ctx, uint64_t n, const mtx_path_planes *camera,
+                                const mtx_path_planes *light, int s, int t, uint32_t max_depth,
+                                uint32_t flags, const uint8_t *active,
+                                float *L /* (3, n) */, float *weight /* (n), may be NULL */);
+/* Host-only and context-free twin of the entry above (like
+ * mtx_blocks_light_host): the same per-lane functions over host planes and a
+ * host scene description, of which it reads the materials, emitters, textures
+ * and tables. MTX_BDPT_VISIBILITY is refused: the library has no host
+ * traversal. Indices outside the tables are handled as none, silently. */
+int mtx_blocks_bdpt_host(const mtx_scene_desc *desc, uint64_t n, const mtx_path_planes *camera,
+                         const mtx_path_planes *light, int s, int t, uint32_t max_depth,
+                         uint32_t flags, float *L, float *weight);
 /* ImageBlock.put (path.py:101): stage 1 of the film (DESIGN.md "Film") for
  * samples the caller holds. The film is the caller's: `planes` are the
  * contribution planes of the band of rows [y0, y1) of a film `width` wide,

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "mtx.h"
+#include "mtx_core/bdpt.h"
 #include "mtx_core/film.h"
 #include "mtx_core/interaction.h"
 #include "blocks.h"
@@ -3266,6 +3267,137 @@ int mtx_blocks_light_host(const mtx_scene_desc *d, int op, uint64_t n, const flo
   }
   mtx_set_error("%s: unknown op %d", fn, op);
   return MTX_E_ARG;
+}
+
+}  // extern "C"
+
+// The arguments the two bdpt entries share: both stores complete and of one
+// depth, the strategy inside it.
+static int bdpt_check(const char *fn, const mtx_path_planes *cam, const mtx_path_planes *lit, int s, int t,
+                      uint32_t max_depth, uint32_t flags, const float *L, const float *weight) {
+  if (!cam || !lit || !L) {
+    mtx_set_error("%s: null argument", fn);
+    return MTX_E_ARG;
+  }
+  for (const mtx_path_planes *q : {cam, lit})
+    if (!q->len || !q->p || !q->n || !q->sh_n || !q->wi || !q->uv || !q->material || !q->emitter || !q->beta ||
+        !q->pdf_fwd || !q->pdf_rev || !q->delta) {
+      mtx_set_error("%s: null plane in the %s store", fn, q == cam ? "camera" : "light");
+      return MTX_E_ARG;
+    }
+  if (cam->depth != lit->depth || cam->depth < 2 || cam->depth > (1u << 16)) {
+    mtx_set_error("%s: depth mismatch: the camera store holds %u vertices per lane, the light store %u (one depth in "
+                  "[2, 65536] expected)", fn, cam->depth, lit->depth);
+    return MTX_E_ARG;
+  }
+  if (max_depth == 0) {
+    mtx_set_error("%s: max_depth = 0 (a path has at least one segment)", fn);
+    return MTX_E_ARG;
+  }
+  if (flags & ~(uint32_t)(MTX_BDPT_MIS | MTX_BDPT_VISIBILITY)) {
+    mtx_set_error("%s: unknown flags 0x%x", fn, flags);
+    return MTX_E_ARG;
+  }
+  const bool all = s == -1 && t == -1;
+  if (all && weight) {
+    mtx_set_error("%s: weight requested with s = t = -1 (a weight belongs to one strategy)", fn);
+    return MTX_E_ARG;
+  }
+  if (!all) {
+    if (t == 0 || t == 1) {
+      mtx_set_error("%s: t = %d: only strategies with t >= 2 exist (t = 1 splats onto the film, t = 0 needs a sensor "
+                    "with an area)", fn, t);
+      return MTX_E_ARG;
+    }
+    if (s < 0 || t < 0 || (uint32_t)s > cam->depth || (uint32_t)t > cam->depth) {
+      mtx_set_error("%s: strategy (s = %d, t = %d) outside the stores' depth %u", fn, s, t, cam->depth);
+      return MTX_E_ARG;
+    }
+  }
+  return MTX_OK;
+}
+
+extern "C" {
+
+int mtx_blocks_bdpt_connect_dev(mtx_ctx *c, uint64_t n, const mtx_path_planes *cam, const mtx_path_planes *lit, int s,
+                                int t, uint32_t max_depth, uint32_t flags, const uint8_t *active, float *L,
+                                float *weight) {
+  const char *fn = "mtx_blocks_bdpt_connect_dev";
+  int rc = blk_begin(c, fn, n, true, {cam, lit, L});
+  if (rc || n == 0) return rc;
+  if ((rc = bdpt_check(fn, cam, lit, s, t, max_depth, flags, L, weight))) return rc;
+  if ((uint64_t)cam->depth * 3 * n >= (1ull << 40)) {
+    mtx_set_error("%s: store too large", fn);
+    return MTX_E_ARG;
+  }
+  for (const mtx_path_planes *q : {cam, lit})
+    if ((rc = need_device(c, fn, {q->len, q->p, q->n, q->sh_n, q->wi, q->uv, q->material, q->emitter, q->beta,
+                                  q->pdf_fwd, q->pdf_rev, q->delta})))
+      return rc;
+  if ((rc = need_device(c, fn, {active, L, weight})) || (rc = blk_bad_reset(c))) return rc;
+  mtxd::launch_blk_bdpt_connect(c->scene, c->scene_n_materials, (uint32_t)n, *cam, *lit, s, t, max_depth, flags,
+                                active, L, weight, (uint32_t *)c->s6.p, c->stream);
+  return blk_end(c, fn, "a vertex whose material or emitter index lies past the scene's tables");
+}
+
+int mtx_blocks_bdpt_host(const mtx_scene_desc *d, uint64_t n, const mtx_path_planes *cam, const mtx_path_planes *lit,
+                         int s, int t, uint32_t max_depth, uint32_t flags, float *L, float *weight) {
+  const char *fn = "mtx_blocks_bdpt_host";
+  if (!d) {
+    mtx_set_error("%s: null argument", fn);
+    return MTX_E_ARG;
+  }
+  if (n >= (1ull << 31)) {
+    mtx_set_error("%s: n >= 2^31", fn);
+    return MTX_E_ARG;
+  }
+  if (flags & MTX_BDPT_VISIBILITY) {
+    mtx_set_error("%s: MTX_BDPT_VISIBILITY: the host twin has no traversal; test visibility on the device", fn);
+    return MTX_E_ARG;
+  }
+  if (n == 0) return MTX_OK;
+  if (int rc = bdpt_check(fn, cam, lit, s, t, max_depth, flags, L, weight)) return rc;
+  if ((d->n_materials && !d->materials) || (d->n_emitters && !d->emitters)) {
+    mtx_set_error("%s: the description lacks its material or emitter array", fn);
+    return MTX_E_ARG;
+  }
+  for (uint32_t i = 0; i < d->n_materials; ++i) {  // what a BSDF evaluation reads, as mtx_scene_upload checks it
+    const mtx_material &m = d->materials[i];
+    if (m.tex >= 0) {
+      if ((uint32_t)m.tex >= d->n_textures || !d->textures || !d->texels ||
+          d->textures[m.tex].offset + 3ull * d->textures[m.tex].width * d->textures[m.tex].height > d->n_texels ||
+          d->textures[m.tex].width == 0 || d->textures[m.tex].height == 0) {
+        mtx_set_error("%s: material %u texture out of range", fn, i);
+        return MTX_E_ARG;
+      }
+    }
+    if (m.type == MTX_MAT_ROUGHPLASTIC &&
+        (m.table < 0 || !d->tables || (uint32_t)m.table + MTX_ROUGH_TRANSMITTANCE_RES > d->n_tables)) {
+      mtx_set_error("%s: roughplastic material %u has no transmittance table", fn, i);
+      return MTX_E_ARG;
+    }
+  }
+  mtx::SceneView sv{};
+  sv.materials = d->materials;
+  sv.emitters = d->emitters;
+  sv.bsdf.textures = d->textures;
+  sv.bsdf.texels = d->texels;
+  sv.bsdf.tables = d->tables;
+  sv.n_tris = d->n_tris;
+  sv.n_emitters = d->n_emitters;
+  sv.has_env = d->has_env ? 1u : 0u;
+  const auto never = [](const mtx::Ray &) { return false; };
+  for (uint64_t i = 0; i < n; ++i) {
+    const mtx::PathLane zc = mtx::path_lane(cam, n, i), yl = mtx::path_lane(lit, n, i);
+    float w = 0.f;
+    const mtx::V3 l = mtx::bdpt_connect(sv, d->n_materials, zc, yl, s, t, max_depth, (flags & MTX_BDPT_MIS) != 0, never,
+                                        &w);
+    L[i] = l.x;
+    L[n + i] = l.y;
+    L[2 * n + i] = l.z;
+    if (weight) weight[i] = w;
+  }
+  return MTX_OK;
 }
 
 }  // extern "C"

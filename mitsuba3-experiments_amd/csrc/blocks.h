@@ -55,6 +55,11 @@ struct SensorDirPlanes {
 void launch_blk_sensor_direction(const DevScene &s, uint32_t n, const float *p, const float *nrm,
                                  const uint8_t *active, int test_visibility, const SensorDirPlanes &out,
                                  hipStream_t st);
+// mtx_blocks_bdpt_connect_dev: strategy (ss, tt) or all (-1, -1) of the two
+// vertex stores per lane; flags MTX_BDPT_*; weight may be null.
+void launch_blk_bdpt_connect(const DevScene &s, uint32_t n_materials, uint32_t n, const mtx_path_planes &camera,
+                             const mtx_path_planes &light, int ss, int tt, uint32_t max_depth, uint32_t flags,
+                             const uint8_t *active, float *L, float *weight, uint32_t *bad, hipStream_t st);
 
 // Film put (mtx_blocks_film_put_dev): the band [y0, y1) of a film `width`
 // wide, its filter, and the contribution planes [slot 8][K][band_px] float4.

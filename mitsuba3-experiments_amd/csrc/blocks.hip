@@ -14,6 +14,7 @@
 
 #include "device_common.h"
 #include "film_dev.h"
+#include "mtx_core/bdpt.h"
 
 namespace mtxd {
 
@@ -335,6 +336,50 @@ __global__ __launch_bounds__(kTraceBlock) void k_blk_sensor_direction(DevScene s
   }
 }
 
+// Connects the camera and light subpaths of a lane (mtx_core/bdpt.h): every
+// strategy, or one, with its weight walk reading the stores' planes; VIS: a
+// connection's shadow ray through the any-hit tree on this thread's stack
+// column, only where the unoccluded contribution is non-zero.
+struct BdptNoShadow {
+  __device__ __forceinline__ bool operator()(const Ray &) const { return false; }
+};
+struct BdptShadow {
+  const DevScene &s;
+  uint32_t *stk;
+  __device__ __forceinline__ bool operator()(const Ray &sr) const {
+    const TraceRay r = make_trace_ray(sr.o, sr.d, sr.maxt);
+    uint32_t nv = 0, tv = 0;
+    return traverse_occ(s, stk, r, sr.maxt, nv, tv);
+  }
+};
+
+template <bool VIS>
+__global__ __launch_bounds__(kTraceBlock) void k_blk_bdpt_connect(DevScene s, uint32_t n_materials, uint32_t n,
+                                                                  mtx_path_planes cam, mtx_path_planes lit, int ss,
+                                                                  int tt, uint32_t max_depth, int mis,
+                                                                  const uint8_t *active, float *L, float *weight,
+                                                                  uint32_t *bad) {
+  extern __shared__ int4 blk_lds[];
+  const SceneView view = make_view(s);  // the counts, before any load that depends on a caller's index
+  const uint32_t n_emitters = view.n_emitters;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    V3 l = v3s(0.f);
+    float w = 0.f;
+    if (lane_on(active, i)) {
+      const PathLane zc = path_lane(&cam, n, i), yl = path_lane(&lit, n, i);
+      if (path_has_bad_index(zc, n_materials, n_emitters) || path_has_bad_index(yl, n_materials, n_emitters))
+        atomicAdd(bad, 1u);
+      if (VIS)
+        l = bdpt_connect(view, n_materials, zc, yl, ss, tt, max_depth, mis != 0,
+                         BdptShadow{s, reinterpret_cast<uint32_t *>(blk_lds) + threadIdx.x}, &w);
+      else
+        l = bdpt_connect(view, n_materials, zc, yl, ss, tt, max_depth, mis != 0, BdptNoShadow{}, &w);
+    }
+    st3(L, n, i, l);
+    if (weight) weight[i] = w;
+  }
+}
+
 // ------------------------------------------------------------------ film --
 // Stage 1 of the film (DESIGN.md "Film") on samples the caller holds. The
 // contribution planes are the fused film's, [slot][K][band_px] float4; a put
@@ -629,6 +674,18 @@ void launch_blk_sensor_direction(const DevScene &s, uint32_t n, const float *p, 
     hipLaunchKernelGGL(k_blk_sensor_direction<true>, grid, block, stack_bytes(s), st, s, n, p, nrm, active, out);
   else
     hipLaunchKernelGGL(k_blk_sensor_direction<false>, grid, block, 0, st, s, n, p, nrm, active, out);
+}
+void launch_blk_bdpt_connect(const DevScene &s, uint32_t n_materials, uint32_t n, const mtx_path_planes &camera,
+                             const mtx_path_planes &light, int ss, int tt, uint32_t max_depth, uint32_t flags,
+                             const uint8_t *active, float *L, float *weight, uint32_t *bad, hipStream_t st) {
+  const dim3 grid(blk_grid(n, kTraceBlock)), block(kTraceBlock);
+  const int mis = (flags & MTX_BDPT_MIS) != 0;
+  if (flags & MTX_BDPT_VISIBILITY)
+    hipLaunchKernelGGL(k_blk_bdpt_connect<true>, grid, block, stack_bytes(s), st, s, n_materials, n, camera, light, ss,
+                       tt, max_depth, mis, active, L, weight, bad);
+  else
+    hipLaunchKernelGGL(k_blk_bdpt_connect<false>, grid, block, 0, st, s, n_materials, n, camera, light, ss, tt,
+                       max_depth, mis, active, L, weight, bad);
 }
 void launch_blk_film_keys(const FilmBand &g, uint32_t n, const float *pos, const uint8_t *active, uint32_t *keys,
                           uint32_t *counts, hipStream_t st) {

@@ -320,10 +320,17 @@ class BsdfPlanes(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("value", "pdf", "s_wo", "s_pdf", "s_eta", "s_type", "weight")]
 
 
+class PathPlanes(C.Structure):
+    """mtx_path_planes: a vertex store of `depth` vertices per lane."""
+    _fields_ = [("depth", C.c_uint32)] + [(k, C.c_void_p) for k in (
+        "len", "p", "n", "sh_n", "wi", "uv", "material", "emitter", "beta", "pdf_fwd", "pdf_rev", "delta")]
+
+
 MTX_MATH_FMA, MTX_MATH_DIV, MTX_MATH_RCP, MTX_MATH_SQRT, MTX_MATH_DOT3 = 0, 1, 2, 3, 4
 MTX_MATH_NORM3, MTX_MATH_NORMALIZE3, MTX_MATH_TO_LOCAL, MTX_MATH_TO_WORLD = 5, 6, 7, 8
 MTX_MATH_MIS_A, MTX_MATH_MIS_B = 9, 10
 MTX_LIGHT_EMITTER_RAY, MTX_LIGHT_SENSOR_DIRECTION, MTX_LIGHT_PROJECT = 0, 1, 2
+MTX_BDPT_MIS, MTX_BDPT_VISIBILITY = 1, 2
 
 # Every symbol include/mtx.h declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -387,6 +394,8 @@ EXPORTS = [
     "mtx_blocks_sample_emitter_ray_dev",
     "mtx_blocks_sensor_direction_dev",
     "mtx_blocks_light_host",
+    "mtx_blocks_bdpt_connect_dev",
+    "mtx_blocks_bdpt_host",
     "mtx_blocks_film_put_dev",
     "mtx_blocks_film_gather_dev",
 ]

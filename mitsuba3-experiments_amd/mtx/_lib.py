@@ -108,6 +108,10 @@ def lib() -> C.CDLL:
         "mtx_blocks_sample_emitter_ray_dev": ([vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "mtx_blocks_sensor_direction_dev": ([vp, u64, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp], C.c_int),
         "mtx_blocks_light_host": ([C.POINTER(_abi.SceneDesc), C.c_int, u64, vp, vp], C.c_int),
+        "mtx_blocks_bdpt_connect_dev": ([vp, u64, C.POINTER(_abi.PathPlanes), C.POINTER(_abi.PathPlanes), C.c_int,
+                                         C.c_int, u32, u32, vp, vp, vp], C.c_int),
+        "mtx_blocks_bdpt_host": ([C.POINTER(_abi.SceneDesc), u64, C.POINTER(_abi.PathPlanes),
+                                  C.POINTER(_abi.PathPlanes), C.c_int, C.c_int, u32, u32, vp, vp], C.c_int),
         "mtx_blocks_film_put_dev": ([vp, vp, u32, u32, u32, u32, u64, vp, vp, vp, u32, u32, u32, u32, C.POINTER(u64)],
                                     C.c_int),
         "mtx_blocks_film_gather_dev": ([vp, vp, u32, u32, u32, u32, vp], C.c_int),

@@ -34,6 +34,11 @@ Paths may also start at the lights: ``Scene.sample_emitter_ray`` emits,
 :class:`AdjointIntegrator` is the render loop that splats through
 ``Film.put``'s general path, and :class:`ParticleTracer` (``"ptracer"``) is
 the estimator built on them.
+
+The two meet in :class:`PathVertices` (a vertex store per subpath),
+:func:`connect_subpaths` (every connection strategy (s, t) with its shadow
+ray and its power-heuristic weight, one kernel; include/mtx_core/bdpt.h) and
+:class:`BidirectionalPathTracer` (``"bdpt"``).
 """
 from __future__ import annotations
 
@@ -1023,3 +1028,356 @@ class ParticleTracer(AdjointIntegrator):
                 inv_q = rcp(torch.where(alive, q, torch.ones_like(q)))
                 throughput, rel = throughput * inv_q, rel * inv_q
             o, d, maxt = si.spawn_ray(wo_w)
+
+
+# ------------------------------------------------- bidirectional connections --
+
+_PATH_PLANES = (("p", 3, "float32"), ("n", 3, "float32"), ("sh_n", 3, "float32"), ("wi", 3, "float32"),
+                ("uv", 2, "float32"), ("material", None, "int32"), ("emitter", None, "int32"),
+                ("beta", 3, "float32"), ("pdf_fwd", None, "float32"), ("pdf_rev", None, "float32"),
+                ("delta", None, "uint8"))
+
+
+def _path_shape(depth, comps, n):
+    return (depth, n) if comps is None else (depth, comps, n)
+
+
+class PathVertices:
+    """A vertex store (``mtx_path_planes``, mtx_core/bdpt.h): one subpath of at
+    most `depth` vertices per lane, every plane coalesced over lanes. ``len``
+    (N, int32); ``p``, ``n``, ``sh_n``, ``wi``, ``beta`` (D, 3, N); ``uv``
+    (D, 2, N); ``material``, ``emitter`` (D, N, int32, -1 = none);
+    ``pdf_fwd``, ``pdf_rev`` (D, N) area-measure densities; ``delta`` (D, N,
+    uint8). All zero (no emitter, no material) until recorded."""
+
+    def __init__(self, device, depth: int, n: int):
+        torch = _torch()
+        depth, n = int(depth), int(n)
+        if depth < 2 or n < 0:
+            raise MtxError(f"PathVertices: depth {depth} (at least 2 vertices) or lane count {n}")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise MtxError(f"PathVertices: device {self.device}; the blocks take CUDA tensors")
+        self.depth, self.lanes = depth, n
+        self.len = torch.zeros(n, dtype=torch.int32, device=self.device)
+        for k, c, dt in _PATH_PLANES:
+            t = torch.zeros(_path_shape(depth, c, n), dtype=getattr(torch, dt), device=self.device)
+            if k in ("material", "emitter"):
+                t -= 1
+            setattr(self, k, t)
+
+    def record(self, k: int, si, beta, pdf_fwd, delta, active) -> None:
+        """Append vertex k = the interaction `si` (p, n, sh_n, wi, uv,
+        material, emitter planes) with the arriving throughput beta (3, N),
+        its forward area density pdf_fwd (N) and the delta flag of the lobe
+        sampled at it (N, bool) to the lanes that are on; ``len`` becomes
+        k + 1 there and nothing changes elsewhere."""
+        torch = _torch()
+        k = int(k)
+        if not 0 <= k < self.depth:
+            raise MtxError(f"record: vertex {k} outside a store of depth {self.depth}")
+        n, dev = self.lanes, self.device
+        for name in ("p", "n", "sh_n", "wi"):
+            _f32(f"record: si.{name}", getattr(si, name), 3, n, dev)
+        _f32("record: si.uv", si.uv, 2, n, dev)
+        _i32("record: si.material", si.material, n, dev)
+        _i32("record: si.emitter", si.emitter, n, dev)
+        _f32("record: beta", beta, 3, n, dev)
+        _f32("record: pdf_fwd", pdf_fwd, None, n, dev)
+        _arg("record: delta", delta, (torch.bool, torch.uint8), None, n, dev)
+        _arg("record: active", active, (torch.bool, torch.uint8), None, n, dev)
+        on = active.bool()
+        for name, src in (("p", si.p), ("n", si.n), ("sh_n", si.sh_n), ("wi", si.wi), ("uv", si.uv),
+                          ("material", si.material), ("emitter", si.emitter), ("beta", beta), ("pdf_fwd", pdf_fwd),
+                          ("delta", delta.to(torch.uint8))):
+            plane = getattr(self, name)[k]
+            plane.copy_(torch.where(on, src, plane))
+        self.len.copy_(torch.where(on, torch.full_like(self.len, k + 1), self.len))
+
+    def set_pdf_rev(self, k: int, pdf) -> None:
+        """The stored reverse density of vertex k (N): with which it would
+        have been generated from vertex k + 1."""
+        k = int(k)
+        if not 0 <= k < self.depth:
+            raise MtxError(f"set_pdf_rev: vertex {k} outside a store of depth {self.depth}")
+        _f32("set_pdf_rev: pdf", pdf, None, self.lanes, self.device)
+        self.pdf_rev[k].copy_(pdf)
+
+    def host(self) -> dict:
+        """The planes as numpy arrays (the layout :func:`bdpt_host` takes)."""
+        out = {k: getattr(self, k).cpu().numpy() for k, _, _ in _PATH_PLANES}
+        out["len"] = self.len.cpu().numpy()
+        return out
+
+
+def _check_store(name, store):
+    """Validate a device store's planes; returns its ctypes mirror."""
+    torch = _torch()
+    if not isinstance(store, PathVertices):
+        raise MtxError(f"{name}: expected a blocks.PathVertices, got {type(store).__name__}")
+    D, n, dev = store.depth, store.lanes, store.device
+    planes = [("len", None, "int32")] + list(_PATH_PLANES)
+    ptrs = {}
+    for k, c, dt in planes:
+        t = getattr(store, k)
+        if not isinstance(t, torch.Tensor):
+            raise MtxError(f"{name}.{k}: expected a torch CUDA tensor, got {type(t).__name__}")
+        if not t.is_cuda:
+            raise MtxError(f"{name}.{k}: a host tensor (device {t.device}); the blocks take CUDA tensors")
+        if t.device != dev:
+            raise MtxError(f"{name}.{k}: on {t.device}, the store is on {dev}")
+        if t.dtype != getattr(torch, dt):
+            raise MtxError(f"{name}.{k}: dtype {t.dtype}, expected torch.{dt}")
+        want = (n,) if k == "len" else _path_shape(D, c, n)
+        if tuple(t.shape) != want:
+            raise MtxError(f"{name}.{k}: shape {tuple(t.shape)}, expected {want}")
+        if not t.is_contiguous():
+            raise MtxError(f"{name}.{k}: not contiguous")
+        ptrs[k] = t.data_ptr()
+    return _abi.PathPlanes(D, *[ptrs[k] for k, _, _ in planes])
+
+
+def _strategy(fn, s, t, max_depth, depth):
+    """(s, t, single) for the ABI; refusals name the cause."""
+    if (s is None) != (t is None):
+        raise MtxError(f"{fn}: s and t: give both (one strategy) or neither (their sum)")
+    if not isinstance(max_depth, (int, np.integer)) or isinstance(max_depth, bool) or max_depth < 1:
+        raise MtxError(f"{fn}: max_depth = {max_depth!r}: expected a segment count >= 1")
+    if s is None:
+        return -1, -1, False
+    s, t = int(s), int(t)
+    if t in (0, 1):
+        raise MtxError(f"{fn}: t = {t}: only strategies with t >= 2 exist (t = 1 splats onto the film)")
+    if s < 0 or t < 0 or s > depth or t > depth:
+        raise MtxError(f"{fn}: strategy (s = {s}, t = {t}) outside the stores' depth {depth}")
+    return s, t, True
+
+
+def connect_subpaths(scene, camera, light, max_depth, s=None, t=None, mis=True, test_visibility=True, active=None):
+    """Join the camera subpaths and the light subpaths of two
+    :class:`PathVertices` lane by lane in one launch (mtx_core/bdpt.h has the
+    conventions). Without s, t: L (3, N), the sum over every strategy (s, t),
+    t >= 2, of s + t - 1 <= max_depth segments, each weighed by the power
+    heuristic (``mis``; else weight 1) and, with ``test_visibility``, zero
+    where the connection's shadow ray is occluded. With s and t: ``(L,
+    weight)`` of that strategy alone."""
+    fn = "connect_subpaths"
+    if not isinstance(scene, Scene):
+        raise MtxError(f"{fn}: scene: expected a blocks.Scene, got {type(scene).__name__}")
+    cam, lit = _check_store(f"{fn}: camera", camera), _check_store(f"{fn}: light", light)
+    if camera.depth != light.depth:
+        raise MtxError(f"{fn}: depth mismatch: camera holds {camera.depth} vertices per lane, light {light.depth}")
+    if camera.lanes != light.lanes:
+        raise MtxError(f"{fn}: light: {light.lanes} lanes, the camera store has N = {camera.lanes}")
+    if camera.device != light.device:
+        raise MtxError(f"{fn}: light: on {light.device}, the camera store is on {camera.device}")
+    n, dev = camera.lanes, camera.device
+    s_, t_, single = _strategy(fn, s, t, max_depth, camera.depth)
+    _, am = _mask(f"{fn}: active", active, n, dev)
+    L = _empty(dev, 3, n)
+    w = _empty(dev, None, n) if single else None
+    if n:
+        flags = (_abi.MTX_BDPT_MIS if mis else 0) | (_abi.MTX_BDPT_VISIBILITY if test_visibility else 0)
+        check(lib().mtx_blocks_bdpt_connect_dev(scene._call(dev), n, C.byref(cam), C.byref(lit), s_, t_,
+                                                int(max_depth), flags, am, L.data_ptr(),
+                                                w.data_ptr() if single else None), "mtx_blocks_bdpt_connect_dev")
+    return (L, w) if single else L
+
+
+def bdpt_host(scene, camera: dict, light: dict, max_depth, s=None, t=None, mis=True, flags=None, want_weight=None):
+    """The CPU twin of :func:`connect_subpaths` (mtx_blocks_bdpt_host): needs
+    no GPU and tests no visibility. ``camera`` / ``light``: dictionaries of
+    numpy planes in :class:`PathVertices`' layout (``PathVertices.host()``).
+    Returns L (3, N), or (L, weight) for one strategy. ``flags`` /
+    ``want_weight`` override what ``mis`` and the strategy imply (the
+    refusals' tests)."""
+    fn = "bdpt_host"
+    keep, mirrors, depth, n = [], [], None, None
+    for name, store in (("camera", camera), ("light", light)):
+        ln = np.ascontiguousarray(store["len"], np.int32)
+        D = int(np.shape(store["pdf_fwd"])[0])
+        if n is None:
+            n = len(ln)
+        ptrs = [ln]
+        for k, c, dt in _PATH_PLANES:
+            a = np.ascontiguousarray(store[k], getattr(np, dt))
+            if a.shape != _path_shape(D, c, n):
+                raise MtxError(f"{fn}: {name}.{k}: shape {a.shape}, expected {_path_shape(D, c, n)}")
+            ptrs.append(a)
+        if len(ln) != n:
+            raise MtxError(f"{fn}: {name}.len: {len(ln)} lanes, the call has N = {n}")
+        keep.append(ptrs)
+        mirrors.append(_abi.PathPlanes(D, *[a.ctypes.data for a in ptrs]))
+        depth = D if depth is None else depth
+    single = s is not None
+    L = np.zeros((3, n), np.float32)
+    w = np.zeros(n, np.float32) if (single if want_weight is None else want_weight) else None
+    if flags is None:
+        flags = _abi.MTX_BDPT_MIS if mis else 0
+    desc = _mtx_scene(scene).desc()
+    check(lib().mtx_blocks_bdpt_host(C.byref(desc), n, C.byref(mirrors[0]), C.byref(mirrors[1]),
+                                     -1 if s is None else int(s), -1 if t is None else int(t), int(max_depth),
+                                     int(flags), L.ctypes.data, None if w is None else w.ctypes.data),
+          "mtx_blocks_bdpt_host")
+    return (L, w) if w is not None else L
+
+
+class _VertexPoint:
+    """A vertex that is no surface hit (the pinhole, an emitter sample) in the
+    planes :meth:`PathVertices.record` reads."""
+
+    def __init__(self, p, n, emitter=None):
+        torch = _torch()
+        cnt, dev = p.shape[1], p.device
+        self.p, self.n, self.sh_n = p, n, n
+        self.wi = torch.zeros((3, cnt), device=dev)
+        self.uv = torch.zeros((2, cnt), device=dev)
+        self.material = torch.full((cnt,), -1, dtype=torch.int32, device=dev)
+        self.emitter = self.material.clone() if emitter is None else emitter
+
+
+class BidirectionalPathTracer(SamplingIntegrator):
+    """A bidirectional path tracer on the blocks (``"bdpt"``): per sample a
+    camera subpath and a light subpath are recorded into two
+    :class:`PathVertices` and joined by one :func:`connect_subpaths` launch,
+    which evaluates every strategy (s, t) with t >= 2 and weighs them with the
+    power heuristic.
+
+    Properties: ``max_depth`` (16, the reference's default; >= 1; counts
+    segments as path_test does), ``rr_depth`` (accepted for the reference's
+    dictionaries and unused: subpaths are not terminated by Russian roulette,
+    which changes the variance and not the expectation), ``rfilter``.
+
+    Not covered: the t = 1 strategies (light paths splatted onto the film:
+    :class:`ParticleTracer`), so a pixel that sees the scene only through a
+    chain of delta surfaces from the light's side gets what its camera paths
+    find; environments and ``roughdielectric`` materials are refused."""
+
+    name = "bdpt"
+
+    def __init__(self, props=None):
+        super().__init__(props)
+        md = self.props.get("max_depth", 16)
+        if isinstance(md, bool) or not isinstance(md, (int, np.integer, float)) or not np.isfinite(md) or md < 1 \
+                or int(md) != md:
+            raise MtxError(f"bdpt: max_depth = {md!r}: expected a finite segment count >= 1")
+        self.max_depth = int(md)
+        self.rr_depth = int(self.props.get("rr_depth", 5))  # unused: no Russian roulette
+
+    def check_scene(self, scene) -> None:
+        sc = _mtx_scene(scene)
+        if getattr(sc, "env_radiance", None) is not None:
+            raise MtxError("bdpt: the scene has a constant environment: an infinite emitter needs its own densities "
+                           "in the weights, which the connection kernel does not have")
+        for i, m in enumerate(sc.materials):
+            if m.type == _abi.MTX_MAT_ROUGHDIELECTRIC:
+                raise MtxError(f"bdpt: material {i} is a roughdielectric: connecting a light path through it needs "
+                               "the adjoint of its BSDF (its eta), which the blocks evaluate in radiance mode only")
+
+    # ------------------------------------------------------------ recording --
+    @staticmethod
+    def _area(pdf_dir, p_from, p_to, n_to):
+        """solid-angle density -> area density at p_to: pdf * |cos| / d^2 (0 where the points coincide)."""
+        torch = _torch()
+        rel = p_to - p_from
+        d2 = (rel * rel).sum(0)
+        some = d2 > 0
+        d2s = torch.where(some, d2, torch.ones_like(d2))
+        cos = torch.abs((n_to * rel).sum(0)) / torch.sqrt(d2s)
+        return torch.where(some, pdf_dir * cos / d2s, torch.zeros_like(d2))
+
+    def _walk(self, scene, sampler, store, k0, last, o, d, maxt, alive, beta, pdf_dir, prev_p, prev_n, adjoint):
+        """Record vertices k0 .. last of a subpath that leaves (prev_p,
+        prev_n) along the ray with the solid-angle density pdf_dir. Returns
+        the validity of the first hit."""
+        torch = _torch()
+        first = None
+        k = k0
+        while k <= last and bool(alive.any()):
+            si = scene.ray_intersect(o, d, maxt, alive)
+            alive = alive & si.valid
+            if first is None:
+                first = alive
+            pdf_fwd = self._area(pdf_dir, prev_p, si.p, si.n)
+            if k == last:  # nothing is sampled at the last vertex
+                store.record(k, si, beta, pdf_fwd, torch.zeros_like(alive), alive)
+                break
+            s1, s2 = sampler.next_1d(), sampler.next_2d()
+            _v, _p, bs, bw = scene.bsdf_eval_pdf_sample(si, si.wi, s1, s2, alive)
+            store.record(k, si, beta, pdf_fwd, (bs.sampled_type & BF_DELTA) != 0, alive)
+            # the reverse density of vertex k - 1: wi and wo exchanged at this vertex
+            rev = SurfaceInteraction.__new__(SurfaceInteraction)
+            rev.material, rev.uv, rev.wi = si.material, si.uv, bs.wo
+            _v, pdf_rev, _bs, _w = scene.bsdf_eval_pdf_sample(rev, si.wi, s1, s2, alive)
+            store.set_pdf_rev(k - 1, torch.where(alive, self._area(pdf_rev, si.p, prev_p, prev_n),
+                                                 torch.zeros_like(pdf_rev)))
+            wo_w = si.to_world(bs.wo)
+            if adjoint:
+                wi_g = dot(si.n, si.to_world(si.wi))
+                ok, corr = ParticleTracer._adjoint(si, wi_g, bs.wo, wo_w)
+                transmitted = (bs.sampled_type & 0x40) != 0  # BF_DELTA_TRANSMISSION: undo the radiance scale
+                bw = torch.where(transmitted, bw * (bs.eta * bs.eta), bw) * corr
+                alive = alive & ok
+            beta = beta * bw
+            alive = alive & (bs.pdf > 0) & (torch.fmax(torch.fmax(beta[0], beta[1]), beta[2]) > 0)
+            o, d, maxt = si.spawn_ray(wo_w)
+            pdf_dir, prev_p, prev_n = bs.pdf, si.p, si.n
+            k += 1
+        return first if first is not None else alive
+
+    def record_camera(self, scene, sampler, ray, store, active=None):
+        """z_0 = the pinhole, z_1 .. the hits along `ray` and its BSDF-sampled
+        continuations, up to max_depth segments. Returns si_1.valid."""
+        torch = _torch()
+        n, dev = sampler.n, sampler.device
+        on = torch.ones(n, dtype=torch.bool, device=dev) if active is None else active.bool()
+        origin = torch.tensor(list(scene.scene.camera.origin), dtype=torch.float32, device=dev)
+        p0 = origin[:, None].expand(3, n).contiguous()
+        zero, one = torch.zeros(n, device=dev), torch.ones((3, n), device=dev)
+        store.record(0, _VertexPoint(p0, torch.zeros((3, n), device=dev)), one, zero, torch.zeros_like(on), on)
+        return self._walk(scene, sampler, store, 1, min(self.max_depth, store.depth - 1), ray.o, ray.d, ray.maxt, on,
+                          one, zero, p0, torch.zeros((3, n), device=dev), False)
+
+    def record_light(self, scene, sampler, store, active=None) -> None:
+        """y_0 = the emitter sample of ``sample_emitter_ray``, y_1 .. the hits
+        of the emitted ray and its continuations with the particle tracer's
+        adjoint handling; y_{s-1} exists for s <= max_depth - 1."""
+        torch = _torch()
+        n, dev = sampler.n, sampler.device
+        ray, weight, es = scene.sample_emitter_ray(sampler.next_2d(), sampler.next_2d(), active)
+        alive = es.emitter >= 0
+        ems = scene.scene.emitters
+        if len(ems) == 0:
+            return
+        inv_area = torch.tensor([float(e.inv_area) for e in ems], dtype=torch.float32, device=dev)
+        pdf_pos = inv_area[es.emitter.clamp(0, len(ems) - 1).long()] * float(np.float32(1.0) / np.float32(len(ems)))
+        le = weight * float(np.float32(1.0 / np.pi))  # radiance / pdf_pos
+        store.record(0, _VertexPoint(es.p, es.n, es.emitter), le, pdf_pos, torch.zeros_like(alive), alive)
+        last = min(self.max_depth - 2, store.depth - 1)
+        if last < 1:
+            return
+        cos0 = torch.clamp((es.n * ray.d).sum(0), min=0.0) * float(np.float32(1.0 / np.pi))
+        self._walk(scene, sampler, store, 1, last, ray.o, ray.d, ray.maxt, alive, weight, cos0, es.p, es.n, True)
+
+    def connect(self, scene, camera, light):
+        """The one launch that joins the two stores; a subclass may pick a strategy."""
+        return connect_subpaths(scene, camera, light, self.max_depth)
+
+    def sample(self, scene, sampler, ray, medium=None, active=None):
+        n, dev = sampler.n, sampler.device
+        cam = PathVertices(dev, self.max_depth + 1, n)
+        lit = PathVertices(dev, self.max_depth + 1, n)
+        valid = self.record_camera(scene, sampler, ray, cam, active)
+        self.record_light(scene, sampler, lit, active)
+        return self.connect(scene, cam, lit), valid, []
+
+    def render_film(self, scene, seed: int = 0, spp: int = 1, y0: int = 0, y1: int | None = None,
+                    spp_total: int | None = None, sample_offset: int = 0, sensor=None, rfilter=None,
+                    max_lanes: int | None = None):
+        """The inherited render loop; ``max_lanes`` defaults to 2^20 lanes per
+        pass: the two stores of max_depth + 1 vertices take about 0.2 KB per
+        vertex and lane."""
+        self.check_scene(scene)
+        return super().render_film(scene, seed=seed, spp=spp, y0=y0, y1=y1, spp_total=spp_total,
+                                   sample_offset=sample_offset, sensor=sensor, rfilter=rfilter,
+                                   max_lanes=1 << 20 if max_lanes is None else max_lanes)

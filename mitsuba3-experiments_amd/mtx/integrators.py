@@ -544,9 +544,10 @@ register_integrator("nerad", lambda props: NeradIntegrator(props))
 
 
 def _register_blocks_integrators() -> None:
-    from .blocks import ParticleTracer
+    from .blocks import BidirectionalPathTracer, ParticleTracer
 
     register_integrator("ptracer", ParticleTracer)  # testpssmlt.py:22-27; written on mtx.blocks
+    register_integrator("bdpt", BidirectionalPathTracer)  # bdpt02.py's dictionary; finished, on mtx.blocks
 
 
 _register_blocks_integrators()

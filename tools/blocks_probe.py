@@ -27,7 +27,14 @@ of the same film and sample count. The frame's scene is the Cornell box of
 tests/blocks_light_cases.py: the bedroom proxy holds a roughdielectric, which
 the particle tracer refuses.
 
-Usage: python tools/blocks_probe.py [--only blocks|film|light] [--log2n 22] [--reps 5] [--scenes small,full] [--out FILE]
+With ``--only bdpt`` (profiles/blocks_bdpt_probe.json; ``--scenes`` is not
+read): for the 32 x 32 and the 256 x 256 Cornell box, one pass of the ``bdpt``
+integrator split into recording the two subpaths and the connect kernel, the
+kernel's strategies per second, and the RMSE of ``bdpt`` and of ``path_test``
+against a long ``path_test`` render at equal wall time on a Cornell variant
+whose light faces the ceiling (all of the room is lit indirectly).
+
+Usage: python tools/blocks_probe.py [--only blocks|film|light|bdpt] [--log2n 22] [--reps 5] [--scenes small,full] [--out FILE]
 """
 import argparse
 import json
@@ -245,28 +252,112 @@ def probe_light(label, sc, n, reps):
                       "ptracer_over_composed": round(ptracer["median_ms"] / comp["median_ms"], 2)}}
 
 
+def probe_bdpt(side, reps, max_depth=8, spp=FILM_SPP):
+    """One bdpt pass on the side x side Cornell box, split; and bdpt against
+    path_test at equal wall time on the variant whose light faces the ceiling."""
+    import copy
+
+    import blocks_light_cases as blc
+    import torch
+    from mtx import blocks, develop, load_dict
+    from mtx.mitsuba_dict import scene_from_dict
+
+    box = scene_from_dict(blc.cornell_dict(side, side))
+    integ = load_dict({"type": "bdpt", "max_depth": max_depth})
+    sens = blocks.Sensor(box)
+    scn = blocks.Scene(sens.scene, sens.ctx.device)
+    n = side * side * spp
+    lanes = torch.arange(n, dtype=torch.int32, device="cuda")
+    pix = torch.arange(side * side, device="cuda").repeat_interleave(spp)
+    state = {}
+
+    def record():
+        sampler = blocks.Sampler(1, lanes)
+        u = sampler.next_2d()
+        pos = torch.stack([(pix % side).float() + u[0], (pix // side).float() + u[1]])
+        cam = blocks.PathVertices(pos.device, max_depth + 1, n)
+        lit = blocks.PathVertices(pos.device, max_depth + 1, n)
+        integ.record_camera(scn, sampler, sens.sample_ray(pos), cam)
+        integ.record_light(scn, sampler, lit)
+        state["stores"] = (cam, lit)
+
+    k = max(3, reps // 2)
+    rec = timed(record, k, 1)
+    cam, lit = state["stores"]
+    con = timed(lambda: blocks.connect_subpaths(scn, cam, lit, max_depth), reps)
+    con_free = timed(lambda: blocks.connect_subpaths(scn, cam, lit, max_depth, test_visibility=False), reps)
+    whole = timed(lambda: integ.render_film(box, seed=1, spp=spp, rfilter="box"), k, 1)
+    lz, ly = cam.len.long(), lit.len.long()
+    strategies = 0
+    for t in range(2, max_depth + 2):
+        strategies += int(((lz >= t) * (torch.clamp(ly, max=max_depth + 1 - t) + 1)).sum())
+    # equal wall time, on the variant whose light faces the ceiling
+    d = copy.deepcopy(blc.cornell_dict(side, side))
+    d["light"]["to_world"] = (blc.translate([0.0, 0.8, 0.01]) @ blc.rotate([1, 0, 0], -90)
+                              @ blc.scale([0.23, 0.19, 0.19]))
+    up = scene_from_dict(d)
+    fused = load_dict({"type": "path_test", "max_depth": max_depth, "rr_depth": max_depth + 1})
+    spp_b = 16
+    t_b = timed(lambda: integ.render_film(up, seed=1, spp=spp_b, rfilter="box"), 3, 1)
+    t_p = timed(lambda: fused.render_film(up, seed=1, spp=256, rfilter="box"), 3, 1)
+    spp_p = max(1, int(round(256 * t_b["median_ms"] / t_p["median_ms"])))
+    t_eq = timed(lambda: fused.render_film(up, seed=1, spp=spp_p, rfilter="box"), 3, 1)
+    ref_spp = 16384 if side <= 64 else 2048
+    ref = np.asarray(develop(fused.render_film(up, seed=999, spp=ref_spp, rfilter="box"), 0), np.float64)
+
+    def rmse(img):
+        return float(np.sqrt(((np.asarray(img, np.float64) - ref) ** 2).mean()))
+
+    e_b = [rmse(develop(integ.render_film(up, seed=10 + i, spp=spp_b, rfilter="box").cpu().numpy(), 0))
+           for i in range(4)]
+    e_p = [rmse(develop(fused.render_film(up, seed=10 + i, spp=spp_p, rfilter="box"), 0)) for i in range(4)]
+    return {"scene": "cornell_box", "film": [side, side], "spp": spp, "lanes": n, "max_depth": max_depth,
+            "pass": {"record_ms": rec, "connect_ms": con, "connect_without_visibility_ms": con_free,
+                     "render_film_ms": whole},
+            "strategies_per_pass": strategies,
+            "strategies_per_s": round(strategies / (con["median_ms"] * 1e-3), 1),
+            "equal_time_light_faces_ceiling": {
+                "reference": {"integrator": "path_test", "spp": ref_spp, "mean": float(ref.mean())},
+                "bdpt": {"spp": spp_b, **t_b, "rmse": [round(e, 5) for e in e_b],
+                         "rmse_mean": round(float(np.mean(e_b)), 5)},
+                "path_test": {"spp": spp_p, **t_eq, "rmse": [round(e, 5) for e in e_p],
+                              "rmse_mean": round(float(np.mean(e_p)), 5)}}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2n", type=int, default=22)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--scenes", default="small,full")
-    ap.add_argument("--only", default="blocks", choices=["blocks", "film", "light"],
+    ap.add_argument("--only", default="blocks", choices=["blocks", "film", "light", "bdpt"],
                     help="blocks: the per-block rows and the composed sample(); film: sensor rays, Film.put / raw "
                          "and the composed render_film (default --out: profiles/blocks_film_probe.json); light: "
-                         "sample_emitter_ray, sample_direction and a ptracer frame (profiles/blocks_light_probe.json)")
+                         "sample_emitter_ray, sample_direction and a ptracer frame (profiles/blocks_light_probe.json); "
+                         "bdpt: a bdpt pass split into recording and connecting, and bdpt against path_test at equal "
+                         "time (profiles/blocks_bdpt_probe.json)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", {"blocks": "blocks_probe.json", "film": "blocks_film_probe.json",
-                                                "light": "blocks_light_probe.json"}[a.only])
+                                                "light": "blocks_light_probe.json",
+                                                "bdpt": "blocks_bdpt_probe.json"}[a.only])
     import torch
     from mtx import scene
 
     if not torch.cuda.is_available():
         raise SystemExit("blocks_probe: needs a GPU (no time is reported from a CPU)")
-    doc = {"probe": {"blocks": "blocks", "film": "blocks film", "light": "blocks light"}[a.only], "hbm_peak_GBps": HBM_PEAK_GBS,
+    doc = {"probe": {"blocks": "blocks", "film": "blocks film", "light": "blocks light", "bdpt": "blocks bdpt"}[a.only],
+           "hbm_peak_GBps": HBM_PEAK_GBS,
            "timing": "host clock around calls that end in a device "
            "synchronise; medians of --reps calls after warm-up", "scenes": []}
+    if a.only == "bdpt":
+        for side in (32, 256):
+            doc["scenes"].append(probe_bdpt(side, a.reps))
+            with open(a.out, "w") as f:
+                json.dump(doc, f, indent=1)
+                f.write("\n")
+        print(json.dumps(doc))
+        return
     for label in a.scenes.split(","):
         sc = scene.bedroom(width=64, height=36, scale=0.02, tex_res=64) if label == "small" else scene.bedroom()
         probe = {"blocks": probe_scene, "film": probe_film, "light": probe_light}[a.only]
