@@ -2,7 +2,7 @@
 // contribution of a strategy (s, t) and its multiple-importance weight
 // (Veach 1997, ch. 10; the power heuristic with exponent 2). Per-lane
 // functions shared by k_blk_bdpt_connect (blocks.hip) and its host twin
-// mtx_blocks_bdpt_host (api.cpp).
+// mtx_blocks_bdpt_host (blocks_entry.cpp).
 //
 // A vertex store (mtx_path_planes, mtx.h) holds one subpath per lane, every
 // plane coalesced over lanes: vertex k, component c of lane i of n lies at

@@ -1,0 +1,167 @@
+// context.cpp — the device context: creation with its environment knobs,
+// destruction, and the buffer, pointer and staging helpers every host file
+// uses (runtime.h).
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "runtime.h"
+
+namespace mtxh {
+
+int dalloc(DevBuf &b, size_t bytes) {
+  if (b.bytes >= bytes && b.p) return MTX_OK;
+  if (b.p) hipFree(b.p);
+  b.p = nullptr;
+  b.bytes = 0;
+  if (bytes == 0) return MTX_OK;
+  hipError_t e = hipMalloc(&b.p, bytes);
+  if (e != hipSuccess) {
+    mtx_set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+    b.p = nullptr;
+    return MTX_E_OOM;
+  }
+  b.bytes = bytes;
+  return MTX_OK;
+}
+
+void dfree(DevBuf &b) {
+  if (b.p) hipFree(b.p);
+  b.p = nullptr;
+  b.bytes = 0;
+}
+
+bool on_device(const mtx_ctx *c, const void *p) {
+  if (!p) return false;
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();  // clear the sticky "invalid value" of an unregistered host pointer
+    return false;
+  }
+  return (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged) && at.device == c->device;
+}
+int need_device(const mtx_ctx *c, const char *fn, std::initializer_list<const void *> ptrs) {
+  int k = 0;
+  for (const void *p : ptrs) {
+    if (p && !on_device(c, p)) {
+      mtx_set_error("%s: argument %d is not device memory of device %d", fn, k, c->device);
+      return MTX_E_ARG;
+    }
+    ++k;
+  }
+  return MTX_OK;
+}
+
+int stage(mtx_ctx *c, DevBuf &slot, size_t bytes, const void *src) {
+  if (int rc = dalloc(slot, bytes)) return rc;
+  if (src) HIP_TRY(hipMemcpyAsync(slot.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+  return MTX_OK;
+}
+int unstage(mtx_ctx *c, std::initializer_list<Unstage> outs) {
+  for (const Unstage &o : outs) HIP_TRY(hipMemcpyAsync(o.dst, o.slot.p, o.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MTX_OK;
+}
+
+}  // namespace mtxh
+
+using namespace mtxh;
+
+// Every environment knob, with its clamp. Read once per context.
+static void read_knobs(Knobs &k) {
+  if (const char *e = getenv("MTX_LDS_STACK")) k.lds_stack = std::max(1, std::min(MTX_BVH_MAX_DEPTH + 1, atoi(e)));
+  if (const char *e = getenv("MTX_LDS_TOP")) k.lds_top = (uint32_t)std::max(0, std::min(256, atoi(e)));
+  if (const char *e = getenv("MTX_OCC_LDS_TOP")) k.occ_lds_top = (uint32_t)std::max(0, std::min(192, atoi(e)));
+  if (const char *e = getenv("MTX_OCC_LDS_STACK"))
+    k.occ_lds_stack = std::max(1, std::min(MTX_BVH_MAX_DEPTH + 1, atoi(e)));
+  if (const char *e = getenv("MTX_STREAMS_MAX_LOG2")) k.streams_max_log2 = (uint32_t)std::max(16, std::min(31, atoi(e)));
+  if (const char *e = getenv("MTX_STREAMS")) k.streams = (uint32_t)std::max(1, std::min(2, atoi(e)));
+  if (const char *e = getenv("MTX_TRACE_BATCH")) k.trace_batch = (uint32_t)std::max(1, std::min(1 << 16, atoi(e)));
+  if (const char *e = getenv("MTX_UREFILL")) k.urefill = (uint32_t)std::max(1, std::min(64, atoi(e)));
+  if (const char *e = getenv("MTX_CAM_UREFILL")) k.cam_urefill = (uint32_t)std::max(1, std::min(64, atoi(e)));
+  if (const char *e = getenv("MTX_OCC_UREFILL")) k.occ_urefill = (uint32_t)std::max(1, std::min(64, atoi(e)));
+  if (const char *e = getenv("MTX_XCD_CLAIM")) k.xcd_claim = atoi(e) != 0;
+  if (const char *e = getenv("MTX_RS_FUSED")) k.rs_fused = atoi(e) ? 1u : 0u;
+  if (const char *e = getenv("MTX_MEGA_PATHS")) k.mega_paths = (uint32_t)strtoul(e, nullptr, 0);
+  if (const char *e = getenv("MTX_CACHE_FUSED")) k.cache_fused = atoi(e) ? 1u : 0u;
+  if (const char *e = getenv("MTX_ENCODE_LM")) k.encode_lm = atoi(e) ? 1u : 0u;
+  if (const char *e = getenv("MTX_CACHE_SORT")) k.cache_sort = (uint32_t)std::max(0, std::min(2, atoi(e)));
+}
+
+extern "C" {
+
+// Diagnostic export (not in mtx.h): the shade kernel's per-phase stamp sums of
+// an MTX_DIAG_STAMPS build (tools/shade_stamps.py); returns the segment
+// count, or -1 in production builds.
+int mtx_diag_shade_stamps(unsigned long long *out) { return mtxd::shade_stamps(out); }
+
+int mtx_ctx_create(int hip_device, mtx_ctx **out) {
+  if (!out) {
+    mtx_set_error("mtx_ctx_create: out is NULL");
+    return MTX_E_ARG;
+  }
+  *out = nullptr;
+  int n = 0;
+  HIP_TRY(hipGetDeviceCount(&n));
+  if (hip_device < 0 || hip_device >= n) {
+    mtx_set_error("mtx_ctx_create: device %d out of range (%d devices)", hip_device, n);
+    return MTX_E_ARG;
+  }
+  HIP_TRY(hipSetDevice(hip_device));
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, hip_device));
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+    mtx_set_error("mtx_ctx_create: device %d is %s, libmtx is built for gfx950", hip_device, prop.gcnArchName);
+    return MTX_E_UNSUPPORTED;
+  }
+  mtx_ctx *c = new mtx_ctx();
+  c->device = hip_device;
+  c->n_cu = prop.multiProcessorCount;
+  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+  if (e != hipSuccess) {
+    delete c;
+    mtx_set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
+    return MTX_E_HIP;
+  }
+  c->wave[0].stream = c->stream;
+  // Persistent grids: every CU filled to the kernels' occupancy (the trace
+  // grid is recomputed per scene: its LDS stack depends on the BVH depth).
+  c->trace_grid = c->closest_grid = c->n_cu * 8;
+  c->shade_grid = c->n_cu * mtxd::shade_blocks_per_cu();
+  {
+    // a gfx950 workgroup may hold the CU's whole 160 KiB of LDS (the attribute
+    // may report the 64 KiB that needs no opt-in; the kernels launch above it)
+    int v = 0;
+    c->max_lds = 160 * 1024;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, hip_device) == hipSuccess &&
+        (size_t)v > c->max_lds)
+      c->max_lds = (size_t)v;
+  }
+  read_knobs(c->knobs);
+  *out = c;
+  return MTX_OK;
+}
+
+void mtx_ctx_destroy(mtx_ctx *c) {
+  if (!c) return;
+  hipSetDevice(c->device);
+  // both streams idle before anything they use goes; wave[0].stream is
+  // c->stream and is destroyed once
+  for (Wave &w : c->wave)
+    if (w.stream) hipStreamSynchronize(w.stream);
+  Wave &w1 = c->wave[1];
+  if (w1.start) hipEventDestroy(w1.start);
+  if (w1.done) hipEventDestroy(w1.done);
+  if (w1.stream) hipStreamDestroy(w1.stream);
+  for (hipEvent_t ev : c->events) hipEventDestroy(ev);
+  if (c->q_pinned) hipHostFree(c->q_pinned);
+  for (hipEvent_t ev : c->prim_ev)
+    if (ev) hipEventDestroy(ev);
+  if (c->stream) hipStreamDestroy(c->stream);
+  delete c;  // every DevBuf member frees its memory (the device is still current)
+}
+
+double mtx_last_device_ms(mtx_ctx *c) { return c ? c->last_device_ms : 0.0; }
+
+}  // extern "C"

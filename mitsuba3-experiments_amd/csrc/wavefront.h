@@ -58,7 +58,7 @@ constexpr uint32_t kOccLdsStack = 8;
 #define MTX_OCC_LDS_TOP 48  // occlusion tree nodes copied into LDS per trace block (0 = none)
 #endif
 #ifndef MTX_CACHE_SORT
-#define MTX_CACHE_SORT 2  // NRC cache query order (api.cpp run_cache): 0 as appended, 1 Morton sort, 2 region x XCD
+#define MTX_CACHE_SORT 2  // NRC cache query order (render.cpp run_cache): 0 as appended, 1 Morton sort, 2 region x XCD
 #endif
 #ifndef MTX_ENCODE_LM
 #define MTX_ENCODE_LM 1  // NRC cache encoder with level-major lanes (field.hip k_field_encode_lm)

@@ -156,3 +156,71 @@ def mesh_tables(scene, em):
     t = np.asarray(scene.tables)[m["offset"]: m["offset"] + 3 * m["count"]]
     n = m["count"]
     return t[:n], t[n: 2 * n], t[2 * n:].view(np.uint32)
+
+
+# ------------------------------------------------- damaged mesh records --
+# One inconsistency each in the "patch" record of the "full" variant:
+# corrupt(sc, em, t, n, box_tri) with t the record's 3 n table floats (pmf | cdf
+# | prim), box_tri a triangle of the box. mtx_scene_upload refuses every one
+# (tests/test_scene_check.py on the host, test_mesh_emitters_gpu.py through a
+# context).
+def _words(sc, em, **change):
+    m = sc.emitters[em].mesh
+    m.update(change)
+    sc.emitters[em].set_mesh(m["offset"], m["count"], m["valid_lo"], m["valid_hi"], m["sum"], m["norm"])
+
+
+def _bad_range(sc, em, t, n, box_tri):
+    _words(sc, em, offset=sc.n_tables - 3 * n + 1)
+
+
+def _bad_triangle_index(sc, em, t, n, box_tri):
+    t[2 * n + 3] = np.array([sc.n_tris], np.uint32).view(np.float32)[0]
+
+
+def _foreign_triangle(sc, em, t, n, box_tri):
+    t[2 * n + 3] = np.array([box_tri], np.uint32).view(np.float32)[0]
+
+
+def _triangle_twice(sc, em, t, n, box_tri):
+    t[2 * n + 3] = t[2 * n + 4]
+
+
+def _decreasing_cdf(sc, em, t, n, box_tri):
+    t[n + 10] = t[n + 8]
+    t[n + 9] = np.nextafter(t[n + 10], np.float32(np.inf))
+
+
+def _zero_sum(sc, em, t, n, box_tri):
+    t[: 2 * n] = 0
+    _words(sc, em, sum=0.0)
+
+
+def _missing_triangle(sc, em, t, n, box_tri):
+    # the last entry dropped: the shape has a triangle the record does not list
+    pmf, cdf, prim = t[:n].copy(), t[n: 2 * n].copy(), t[2 * n: 3 * n].copy()
+    m = n - 1
+    t[:m], t[m: 2 * m], t[2 * m: 3 * m] = pmf[:m], cdf[:m], prim[:m]
+    _words(sc, em, count=m, valid_hi=m - 1, sum=float(cdf[m - 1]), norm=float(np.float32(1) / cdf[m - 1]))
+
+
+MESH_RECORD_CORRUPTIONS = [(_bad_range, "table range"), (_bad_triangle_index, "names triangle"),
+                           (_foreign_triangle, "another emitter or none"), (_triangle_twice, "listed twice"),
+                           (_decreasing_cdf, "decreasing cdf"), (_zero_sum, "positive finite sum"),
+                           (_missing_triangle, "does not list")]
+
+
+def with_corrupt_patch(good, corrupt):
+    """A copy of the "full" scene `good` with its own tables and emitter
+    records, the patch's record damaged by `corrupt`."""
+    import copy
+
+    em = emitter_of(good, "patch")
+    sc = copy.copy(good)
+    sc.tables = np.array(good.tables, np.float32)
+    sc.emitters = type(good.emitters).from_buffer_copy(bytes(good.emitters))
+    m = sc.emitters[em].mesh
+    n = m["count"]
+    box_tri = int(np.flatnonzero(np.asarray(good.tri_shape) == 0)[0])
+    corrupt(sc, em, sc.tables[m["offset"]: m["offset"] + 3 * n], n, box_tri)
+    return sc

@@ -145,7 +145,7 @@ def test_nrc_cache_film_bit_exact(small_scene, oracle, chunk):
 def test_nrc_cache_deep_field_bit_exact(small_scene, oracle, n_hidden):
     """Fields deeper than the fused cache kernel's LDS allows (n_hidden 15 /
     16 need more than the 160 KiB of a workgroup) take the three-kernel path
-    (encode, MLP, apply; api.cpp run_cache) instead of a failed launch: the
+    (encode, MLP, apply; render.cpp run_cache) instead of a failed launch: the
     film still equals the oracle's composition bit for bit; n_hidden 14 is
     the deepest fused case."""
     from mtx import load_dict

@@ -151,7 +151,7 @@ def test_render_film_bit_exact(small_scene, oracle, name):
 @pytest.mark.parametrize("name", ["path_test", "mypath", "nrc"])
 def test_two_stream_chunks_bit_exact(small_scene, oracle, name):
     """Renders of >= 2^16 paths alternate their chunks between two wavefronts
-    on two HIP streams (api.cpp Wave, wave[0] / wave[1]): 7 chunks of 5 rows (boundaries inside
+    on two HIP streams (runtime.h Wave, wave[0] / wave[1]): 7 chunks of 5 rows (boundaries inside
     the sample range of no pixel, an odd count, a short last chunk) give the
     oracle's film bit for bit, as does the default two-chunk split."""
     from mtx import load_dict

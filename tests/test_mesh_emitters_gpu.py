@@ -4,8 +4,9 @@ emitter vertex, the ReSTIR GI secondary paths in the wavefront and in the path
 megakernel) bit for bit against the oracle, on the fixture of
 tests/mesh_emitter_cases.py and its variants. The 198-triangle patch is in
 every scene, so the lanes of a wave search its cdf along different paths.
-mtx_scene_upload's checks of a mesh record are here too: they sit behind
-context creation."""
+mtx_scene_upload's refusals of a damaged mesh record and of a bad tree are
+here as a context's caller sees them; tests/test_scene_check.py pins the host
+check itself, case by case, without a GPU."""
 import copy
 import ctypes as C
 import os
@@ -226,50 +227,7 @@ def test_rebinding_serves_the_new_emitters(fx, oracle):
 
 
 # -------------------------------------------------------- upload validation --
-def _words(sc, em, **change):
-    m = sc.emitters[em].mesh
-    m.update(change)
-    sc.emitters[em].set_mesh(m["offset"], m["count"], m["valid_lo"], m["valid_hi"], m["sum"], m["norm"])
-
-
-def _bad_range(sc, em, t, n, box_tri):
-    _words(sc, em, offset=sc.n_tables - 3 * n + 1)
-
-
-def _bad_triangle_index(sc, em, t, n, box_tri):
-    t[2 * n + 3] = np.array([sc.n_tris], np.uint32).view(np.float32)[0]
-
-
-def _foreign_triangle(sc, em, t, n, box_tri):
-    t[2 * n + 3] = np.array([box_tri], np.uint32).view(np.float32)[0]
-
-
-def _triangle_twice(sc, em, t, n, box_tri):
-    t[2 * n + 3] = t[2 * n + 4]
-
-
-def _decreasing_cdf(sc, em, t, n, box_tri):
-    t[n + 10] = t[n + 8]
-    t[n + 9] = np.nextafter(t[n + 10], np.float32(np.inf))
-
-
-def _zero_sum(sc, em, t, n, box_tri):
-    t[: 2 * n] = 0
-    _words(sc, em, sum=0.0)
-
-
-def _missing_triangle(sc, em, t, n, box_tri):
-    # the last entry dropped: the shape has a triangle the record does not list
-    pmf, cdf, prim = t[:n].copy(), t[n: 2 * n].copy(), t[2 * n: 3 * n].copy()
-    m = n - 1
-    t[:m], t[m: 2 * m], t[2 * m: 3 * m] = pmf[:m], cdf[:m], prim[:m]
-    _words(sc, em, count=m, valid_hi=m - 1, sum=float(cdf[m - 1]), norm=float(np.float32(1) / cdf[m - 1]))
-
-
-@pytest.mark.parametrize("corrupt,match", [(_bad_range, "table range"), (_bad_triangle_index, "names triangle"),
-                                           (_foreign_triangle, "another emitter or none"),
-                                           (_triangle_twice, "listed twice"), (_decreasing_cdf, "decreasing cdf"),
-                                           (_zero_sum, "positive finite sum"), (_missing_triangle, "does not list")])
+@pytest.mark.parametrize("corrupt,match", mc.MESH_RECORD_CORRUPTIONS)
 def test_upload_refuses_inconsistent_mesh_records(fx, corrupt, match):
     """mtx_scene_upload checks a mesh record on the host before anything
     reaches the device: each inconsistency is MTX_E_ARG with a message, and
@@ -278,17 +236,38 @@ def test_upload_refuses_inconsistent_mesh_records(fx, corrupt, match):
     from mtx._lib import lib
 
     good = mc.build(fx, "full", W, H)
-    em = mc.emitter_of(good, "patch")
-    sc = copy.copy(good)
-    sc.tables = np.array(good.tables, np.float32)
-    sc.emitters = type(good.emitters).from_buffer_copy(bytes(good.emitters))
-    m = sc.emitters[em].mesh
-    n = m["count"]
-    box_tri = int(np.flatnonzero(np.asarray(good.tri_shape) == 0)[0])
-    corrupt(sc, em, sc.tables[m["offset"]: m["offset"] + 3 * n], n, box_tri)
+    sc = mc.with_corrupt_patch(good, corrupt)
     d = sc.desc()
     rc = lib().mtx_scene_upload(context(0).handle, C.byref(d))
     assert rc < 0 and _abi.ERRORS[rc] == "MTX_E_ARG"
     assert match in lib().mtx_last_error().decode()
     integ = load_dict({"type": "path_test", "max_depth": 4})
     assert integ.render_film(good, seed=0, spp=1)[..., 3].sum() > 0
+
+
+def test_upload_refuses_a_bad_tree_and_keeps_the_scene(fx):
+    """A structural refusal reaches mtx_scene_upload's caller with the words of
+    the host check (tests/test_scene_check.py pins every such refusal on the
+    CPU), no kernel sees the bad tree, and the scene bound before the refused
+    call renders the same film after it."""
+    from mtx import _abi, context, load_dict
+    from mtx._lib import lib
+
+    good = mc.build(fx, "full", 64, 36)
+    integ = load_dict({"type": "path_test"})
+    before = integ.render_film(good, seed=0, spp=1)
+    sc = copy.copy(good)
+    sc.nodes = np.array(good.nodes, np.int32)
+    k = int(np.flatnonzero(sc.nodes.reshape(-1, 16)[0, 4:8] >= 0)[0])  # an inner child of the root
+    sc.nodes[4 + k] = sc.n_nodes
+    d = sc.desc()
+    check = lib().mtx_diag_scene_check
+    check.argtypes, check.restype = [C.POINTER(_abi.SceneDesc), C.POINTER(C.c_uint32)], C.c_int
+    rc = check(C.byref(d), None)
+    said = lib().mtx_last_error().decode()
+    assert rc < 0 and _abi.ERRORS[rc] == "MTX_E_ARG" and "out of range" in said
+    rc = lib().mtx_scene_upload(context(0).handle, C.byref(d))
+    assert rc < 0 and _abi.ERRORS[rc] == "MTX_E_ARG"
+    assert lib().mtx_last_error().decode() == said
+    np.testing.assert_array_equal(integ.render_film(good, seed=0, spp=1), before)
+    assert before[..., 3].sum() > 0

@@ -123,7 +123,7 @@ def test_restir_moving_camera_bit_exact(small_scene, oracle):
 @pytest.mark.gpu
 def test_restir_two_wavefront_split_bit_exact(small_scene, oracle):
     """A frame of >= 2^16 lanes runs stage A as two row halves on two
-    wavefronts / streams (api.cpp render_restir): 384x216 (82,944 lanes), a
+    wavefronts / streams (render.cpp render_restir): 384x216 (82,944 lanes), a
     moving camera, films and temporal reservoirs bit-exact vs the oracle."""
     from mtx import _abi, load_dict
 
