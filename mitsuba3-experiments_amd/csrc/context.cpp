@@ -68,8 +68,9 @@ int unstage(mtx_ctx *c, std::initializer_list<Unstage> outs) {
 
 using namespace mtxh;
 
-// Every environment knob, with its clamp. Read once per context.
-static void read_knobs(Knobs &k) {
+// Every environment knob, with its clamp. Read once per context. False (and
+// the error set): a value that has no clamp to fall back on.
+static bool read_knobs(Knobs &k) {
   if (const char *e = getenv("MTX_LDS_STACK")) k.lds_stack = std::max(1, std::min(MTX_BVH_MAX_DEPTH + 1, atoi(e)));
   if (const char *e = getenv("MTX_LDS_TOP")) k.lds_top = (uint32_t)std::max(0, std::min(256, atoi(e)));
   if (const char *e = getenv("MTX_OCC_LDS_TOP")) k.occ_lds_top = (uint32_t)std::max(0, std::min(192, atoi(e)));
@@ -81,12 +82,22 @@ static void read_knobs(Knobs &k) {
   if (const char *e = getenv("MTX_UREFILL")) k.urefill = (uint32_t)std::max(1, std::min(64, atoi(e)));
   if (const char *e = getenv("MTX_CAM_UREFILL")) k.cam_urefill = (uint32_t)std::max(1, std::min(64, atoi(e)));
   if (const char *e = getenv("MTX_OCC_UREFILL")) k.occ_urefill = (uint32_t)std::max(1, std::min(64, atoi(e)));
+  if (const char *e = getenv("MTX_TRACE_RING")) {
+    char *end = nullptr;
+    const long v = strtol(e, &end, 10);
+    if (end == e || *end || !mtxd::ring_size_ok(v)) {
+      mtx_set_error("MTX_TRACE_RING=%s: the ring holds 0 (none), 16 or 32 rays", e);
+      return false;
+    }
+    k.trace_ring = (uint32_t)v;
+  }
   if (const char *e = getenv("MTX_XCD_CLAIM")) k.xcd_claim = atoi(e) != 0;
   if (const char *e = getenv("MTX_RS_FUSED")) k.rs_fused = atoi(e) ? 1u : 0u;
   if (const char *e = getenv("MTX_MEGA_PATHS")) k.mega_paths = (uint32_t)strtoul(e, nullptr, 0);
   if (const char *e = getenv("MTX_CACHE_FUSED")) k.cache_fused = atoi(e) ? 1u : 0u;
   if (const char *e = getenv("MTX_ENCODE_LM")) k.encode_lm = atoi(e) ? 1u : 0u;
   if (const char *e = getenv("MTX_CACHE_SORT")) k.cache_sort = (uint32_t)std::max(0, std::min(2, atoi(e)));
+  return true;
 }
 
 extern "C" {
@@ -95,6 +106,21 @@ extern "C" {
 // an MTX_DIAG_STAMPS build (tools/shade_stamps.py); returns the segment
 // count, or -1 in production builds.
 int mtx_diag_shade_stamps(unsigned long long *out) { return mtxd::shade_stamps(out); }
+
+// Diagnostic export (not in mtx.h; needs no device): the LDS bytes of a
+// k_trace_closest block with rings of `ring` rays, for a tree deeper and
+// larger than the knobs ask for: out[0], and out[1] the stack entries it
+// keeps in LDS -- mtx_scene_upload's split (scene.cpp) on the knobs' values.
+int mtx_diag_trace_lds(uint32_t ring, uint32_t lds_stack, uint32_t lds_top, uint32_t *out) {
+  if (!out || !mtxd::ring_size_ok(ring) || !lds_stack) return MTX_E_ARG;
+  mtxd::DevScene s{};
+  s.lds_entries = lds_stack;
+  s.lds_top = lds_top;
+  mtxd::split_trace_lds(s, ring);
+  out[0] = (uint32_t)mtxd::ring_stack_bytes(s);
+  out[1] = s.ring_lds_entries;
+  return MTX_OK;
+}
 
 int mtx_ctx_create(int hip_device, mtx_ctx **out) {
   if (!out) {
@@ -138,7 +164,10 @@ int mtx_ctx_create(int hip_device, mtx_ctx **out) {
         (size_t)v > c->max_lds)
       c->max_lds = (size_t)v;
   }
-  read_knobs(c->knobs);
+  if (!read_knobs(c->knobs)) {
+    mtx_ctx_destroy(c);
+    return MTX_E_ARG;
+  }
   *out = c;
   return MTX_OK;
 }

@@ -5,6 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "mtx_core/bsdf.h"
 #include "mtx_core/geometry.h"
 #include "mtx_core/interaction.h"
@@ -27,15 +29,7 @@ inline size_t stack_bytes(const DevScene &s) {
   const size_t a = s.stack_entries, b = 2 * (size_t)s.occ_stack_entries;
   return (a > b ? a : b) * sizeof(uint32_t) * kTraceBlock;
 }
-// The persistent kernels keep only the top lds_entries entries in LDS (so
-// LDS does not cap occupancy) and spill deeper entries to a per-thread global
-// area ([entry - lds_entries][thread], coalesced per depth), rarely touched.
-// Behind the stack columns each block holds an LDS copy of the first lds_top
-// nodes of its tree (the top of the breadth-first tree).
-inline size_t persistent_stack_bytes(const DevScene &s, bool occ) {
-  return occ ? (size_t)s.occ_lds_entries * kTraceBlock * sizeof(uint2) + (size_t)s.occ_lds_top * 80
-             : (size_t)s.lds_entries * kTraceBlock * sizeof(int32_t) + (size_t)s.lds_top * 64;
-}
+// The persistent kernels' LDS: wavefront.h persistent_stack_bytes.
 
 __device__ __forceinline__ SceneView make_view(const DevScene &s) {
   SceneView v;
@@ -510,7 +504,8 @@ __device__ __forceinline__ bool traverse_occ(const DevScene &s, uint32_t *stk, c
 // if it holds triangles to test; nothing waits for the slowest lane of the
 // wave to reach a leaf. Finished lanes are refilled from a per-wave
 // reservoir of claimed queue indices once s.urefill lanes of the wave are
-// idle -- one device-scope atomic per claimed batch. Waves claim rays from
+// idle (k_trace_closest: from the wave's ring of prepared rays, at once;
+// RayRing below) -- one device-scope atomic per claimed batch. Waves claim rays from
 // their own XCD's eighth of the queue first (that XCD's L2 then holds the
 // band's nodes). Each ray's visit sequence is the oracle's, with or without
 // STATS. Src provides: a Payload type (what a lane carries for its ray),
@@ -624,6 +619,74 @@ struct RayReservoir {
   }
 };
 
+// A wave's ring of prepared rays in LDS (the RING form of the closest-hit
+// loop: k_trace_closest; measured slower for the camera source and for any
+// hit). Whenever the ring is empty and the reservoir is
+// not, lanes 0..R-1 -- with or without a ray of their own -- each take a
+// queue index, run Src::load into temporaries and park the TraceRay and the
+// payload (one word: the queue position) in slot `lane`; a lane that finishes
+// takes the slot of its rank among the idle lanes in the same iteration, so
+// no lane waits for a refill threshold and the set-up (the ray loads,
+// make_trace_ray's three divisions) always runs R lanes wide. An entry is
+// kRingWords = 14 words in four planes, slot i of a plane at i x its width:
+// o | maxt, d | payload, idir | ooi.x (16 B each: conflict-free
+// ds_write_b128 / ds_read_b128) and ooi.yz (8 B). Head and count are
+// wave-uniform; only the wave itself touches its ring, in program order, so
+// there is no barrier and no atomic.
+struct RayRing {
+  static_assert(kRingWords == 14, "three 16-B planes and an 8-B one");
+  uint32_t *base;  // this wave's slots
+  uint32_t R, head, n;
+
+  __device__ __forceinline__ void put(uint32_t i, const TraceRay &r, uint32_t payload) const {
+    float4 *p = reinterpret_cast<float4 *>(base);
+    p[i] = make_float4(r.o.x, r.o.y, r.o.z, r.maxt);
+    p[R + i] = make_float4(r.d.x, r.d.y, r.d.z, __uint_as_float(payload));
+    p[2 * R + i] = make_float4(r.idir.x, r.idir.y, r.idir.z, r.ooi.x);
+    reinterpret_cast<float2 *>(p + 3 * R)[i] = make_float2(r.ooi.y, r.ooi.z);
+  }
+  __device__ __forceinline__ void get(uint32_t i, TraceRay &r, uint32_t &payload) const {
+    const float4 *p = reinterpret_cast<const float4 *>(base);
+    const float4 a = p[i], b = p[R + i], c = p[2 * R + i];
+    const float2 e = reinterpret_cast<const float2 *>(p + 3 * R)[i];
+    r.o = V3{a.x, a.y, a.z};
+    r.maxt = a.w;
+    r.d = V3{b.x, b.y, b.z};
+    payload = __float_as_uint(b.w);
+    r.idir = V3{c.x, c.y, c.z};
+    r.ooi = V3{c.w, e.x, e.y};
+  }
+
+  // Produce (ring empty, reservoir not): a whole fill, or what the queue has left.
+  template <class Src>
+  __device__ __forceinline__ void fill(const DevScene &s, const Src &src, RayReservoir &res, uint32_t lane) {
+    static_assert(std::is_same<typename Src::Payload, uint32_t>::value, "a ring entry has one payload word");
+    uint32_t k;
+    bool ok;
+    res.take(s, (1ull << R) - 1ull, lane, k, ok);
+    const bool mine = lane < R && ok;  // the lanes that got an index are a prefix of 0..R-1
+    if (mine) {
+      TraceRay r;
+      float tmax;
+      uint32_t payload;
+      src.load(k, r, tmax, payload);  // tmax == r.maxt
+      put(lane, r, payload);
+    }
+    head = 0;
+    n = (uint32_t)__popcll(__ballot(mine));
+  }
+  // Consume: the idle lane of rank rk < n takes slot head + rk (true: r, payload are its new ray's).
+  __device__ __forceinline__ bool pop(uint64_t idle, bool is_idle, TraceRay &r, uint32_t &payload) {
+    const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+    const bool got = is_idle && rk < n;
+    if (got) get(head + rk, r, payload);
+    const uint32_t taken = min((uint32_t)__popcll(idle), n);
+    head += taken;
+    n -= taken;
+    return got;
+  }
+};
+
 __device__ __forceinline__ void count_wave_iter(uint32_t lane, uint32_t *ctr) {
   const uint64_t m = __ballot(true);
   if (lane == (uint32_t)(__ffsll((unsigned long long)m) - 1)) ++*ctr;
@@ -633,10 +696,10 @@ __device__ __forceinline__ void count_wave_iter(uint32_t lane, uint32_t *ctr) {
 // visit or a leaf's triangle range; a visit pushes the far hit children
 // (three unconditional LDS stores when they fit: dead entries above the new
 // top are harmless) and continues with the nearest.
-template <bool STATS, class Src>
+template <bool STATS, bool RING, class Src>
 __device__ __forceinline__ void trace_loop_closest(const DevScene &s, const Src &src, uint32_t count, uint32_t *heads,
-                                                   int32_t *stk, const int4 *top, uint32_t &nv, uint32_t &tv,
-                                                   uint32_t &nr, uint32_t *wave_iters) {
+                                                   int32_t *stk, const int4 *top, uint32_t *ring, uint32_t &nv,
+                                                   uint32_t &tv, uint32_t &nr, uint32_t *wave_iters) {
   const uint32_t lane = lane_id();
   int32_t *ovf = reinterpret_cast<int32_t *>(s.stack_ovf) + blockIdx.x * kTraceBlock + threadIdx.x;
   const int lds_n = (int)s.lds_entries, top_n = (int)s.lds_top;
@@ -707,8 +770,25 @@ __device__ __forceinline__ void trace_loop_closest(const DevScene &s, const Src 
         pop_next();
       }
   };
+  // a lane starts the ray it was given
+  auto begin_ray = [&]() {
+    prim = 0xffffffffu;
+    bu = bv = 0.f;
+    node = 0;
+    tri = tri_end = 0;
+    sp = 0;
+    has = true;
+  };
+  [[maybe_unused]] RayRing rr{ring, s.trace_ring, 0, 0};  // RING
   while (true) {
-    if (!res.exhausted) {
+    if constexpr (RING) {
+      if (rr.n == 0 && !res.exhausted) rr.fill(s, src, res, lane);
+      const uint64_t idle = __ballot(!has);
+      if (rr.n != 0 && idle != 0 && rr.pop(idle, !has, r, payload)) {
+        tbest = r.maxt;
+        begin_ray();
+      }
+    } else if (!res.exhausted) {
       const uint64_t idle = __ballot(!has);
       if ((uint32_t)__popcll(idle) >= s.urefill || idle == ~0ull) {
         uint32_t k;
@@ -716,12 +796,7 @@ __device__ __forceinline__ void trace_loop_closest(const DevScene &s, const Src 
         res.take(s, idle, lane, k, ok);
         if (!has && ok) {
           src.load(k, r, tbest, payload);
-          prim = 0xffffffffu;
-          bu = bv = 0.f;
-          node = 0;
-          tri = tri_end = 0;
-          sp = 0;
-          has = true;
+          begin_ray();
         }
       }
     }
@@ -848,9 +923,10 @@ __device__ __forceinline__ void trace_loop_occ(const DevScene &s, const Src &src
 
 // The persistent traversal of a block: ANY = any hit on the occlusion tree,
 // else closest hit on the 4-wide tree. The block's dynamic LDS holds the
-// stack columns and then the tree top (persistent_stack_bytes), filled here
-// behind a barrier; every thread of the block calls this.
-template <bool ANY, bool STATS = false, class Src>
+// stack columns, then the tree top (persistent_stack_bytes), filled here
+// behind a barrier, then the waves' prepared-ray rings of a RING kernel;
+// every thread of the block calls this.
+template <bool ANY, bool STATS = false, bool RING = false, class Src>
 __device__ __forceinline__ void trace_loop(const DevScene &s, const Src &src, uint32_t count, uint32_t *heads,
                                            uint32_t &nv, uint32_t &tv, uint32_t &nr,
                                            uint32_t *wave_iters = nullptr) {
@@ -863,6 +939,7 @@ __device__ __forceinline__ void trace_loop(const DevScene &s, const Src &src, ui
     if (blockIdx.x * (kTraceBlock / 64u) >= (count + batch - 1) / batch) return;
   }
   if (ANY) {
+    static_assert(!(ANY && RING), "the any-hit loop has no ring");
     uint2 *cols = reinterpret_cast<uint2 *>(trace_lds);
     int4 *top = reinterpret_cast<int4 *>(cols + s.occ_lds_entries * kTraceBlock);
     for (uint32_t i = threadIdx.x; i < 5 * s.occ_lds_top; i += kTraceBlock) top[i] = s.occ_nodes[i];
@@ -873,7 +950,12 @@ __device__ __forceinline__ void trace_loop(const DevScene &s, const Src &src, ui
     int4 *top = reinterpret_cast<int4 *>(cols + s.lds_entries * kTraceBlock);
     for (uint32_t i = threadIdx.x; i < 4 * s.lds_top; i += kTraceBlock) top[i] = s.nodes[i];
     __syncthreads();
-    trace_loop_closest<STATS>(s, src, count, heads, cols + threadIdx.x, top, nv, tv, nr, wave_iters);
+    // this wave's ring: R entries behind the top (16-B aligned: R is a multiple of 4)
+    uint32_t *ring = nullptr;
+    if constexpr (RING)
+      ring = reinterpret_cast<uint32_t *>(top + 4 * s.lds_top) +
+             __builtin_amdgcn_readfirstlane(threadIdx.x / 64u) * s.trace_ring * kRingWords;
+    trace_loop_closest<STATS, RING>(s, src, count, heads, cols + threadIdx.x, top, ring, nv, tv, nr, wave_iters);
   }
 }
 

@@ -74,13 +74,15 @@ struct ClosestSrc {
 #ifndef MTX_CLOSEST_WAVES
 #define MTX_CLOSEST_WAVES 8  // closest hit: waves/SIMD the register budget is sized for
 #endif
-template <bool STATS>
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MTX_CLOSEST_WAVES))) void k_trace_closest(DevScene s, WaveBuffers b, uint32_t bounce) {
-  // dynamic LDS: stack columns + tree top (device_common.h trace_loop)
+// RING: idle lanes take prepared rays from the wave's LDS ring (device_common.h
+// RayRing), else the threshold refill.
+template <bool STATS, bool RING>
+__device__ __forceinline__ void trace_closest_body(const DevScene &s, const WaveBuffers &b, uint32_t bounce) {
+  // dynamic LDS: stack columns + tree top + rings (device_common.h trace_loop)
   const uint32_t rp = (bounce + b.ray_par) & 1u;
   const ClosestSrc src{b, b.queue[bounce & 1], b.ray_o[rp], b.ray_d[rp]};
   uint32_t nv = 0, tv = 0, nr = 0, wi[2] = {0, 0};
-  trace_loop<false, STATS>(s, src, b.counters[4 * bounce + 0], b.xheads + (2 * bounce) * kXSlotWords, nv, tv, nr,
+  trace_loop<false, STATS, RING>(s, src, b.counters[4 * bounce + 0], b.xheads + (2 * bounce) * kXSlotWords, nv, tv, nr,
                            wi);
   if (STATS) {
     unsigned long long a = wave_sum_u64(nv), c = wave_sum_u64(tv), n = wave_sum_u64(nr);
@@ -93,6 +95,17 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MTX
       atomicAdd(&b.stats[7], w1);
     }
   }
+}
+// The closest-hit kernel: prepared-ray rings (DevScene::trace_ring rays per wave).
+template <bool STATS>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MTX_CLOSEST_WAVES))) void k_trace_closest(DevScene s, WaveBuffers b, uint32_t bounce) {
+  trace_closest_body<STATS, true>(s, b, bounce);
+}
+// MTX_TRACE_RING=0: the same loop with the threshold refill (DevScene::urefill),
+// the reference the ring is measured and tested against.
+template <bool STATS>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MTX_CLOSEST_WAVES))) void k_trace_closest_refill(DevScene s, WaveBuffers b, uint32_t bounce) {
+  trace_closest_body<STATS, false>(s, b, bounce);
 }
 
 // A shadow record's contribution to its path's L (T, X and flags of
@@ -1903,13 +1916,22 @@ void launch_raygen_rays(const DevScene &s, const WaveBuffers &b, const ChunkPara
   hipLaunchKernelGGL(k_raygen_rays, dim3(blocks_for(p.n_paths, 256)), dim3(256), 0, st, s, b, p, rays, lanes,
                      rng_skip);
 }
-void launch_trace_closest(const DevScene &s, const WaveBuffers &b, uint32_t bounce, uint32_t stats, int grid,
+void launch_trace_closest(const DevScene &scene, const WaveBuffers &b, uint32_t bounce, uint32_t stats, int grid,
                           hipStream_t st) {
-  const size_t lds = persistent_stack_bytes(s, false);
+  if (scene.trace_ring) {
+    const DevScene s = ring_view(scene);
+    const size_t lds = ring_stack_bytes(scene);
+    if (stats)
+      hipLaunchKernelGGL(k_trace_closest<true>, dim3(grid), dim3(kTraceBlock), lds, st, s, b, bounce);
+    else
+      hipLaunchKernelGGL(k_trace_closest<false>, dim3(grid), dim3(kTraceBlock), lds, st, s, b, bounce);
+    return;
+  }
+  const size_t lds = persistent_stack_bytes(scene, false);
   if (stats)
-    hipLaunchKernelGGL(k_trace_closest<true>, dim3(grid), dim3(kTraceBlock), lds, st, s, b, bounce);
+    hipLaunchKernelGGL(k_trace_closest_refill<true>, dim3(grid), dim3(kTraceBlock), lds, st, scene, b, bounce);
   else
-    hipLaunchKernelGGL(k_trace_closest<false>, dim3(grid), dim3(kTraceBlock), lds, st, s, b, bounce);
+    hipLaunchKernelGGL(k_trace_closest_refill<false>, dim3(grid), dim3(kTraceBlock), lds, st, scene, b, bounce);
 }
 void launch_trace_camera(const DevScene &scene, const WaveBuffers &b, const ChunkParams &p, int grid, hipStream_t st) {
   DevScene s = scene;
@@ -1983,9 +2005,12 @@ int trace_blocks_per_cu(const DevScene &s) {
 }
 int closest_blocks_per_cu(const DevScene &s) {
   int nc = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nc, k_trace_closest<false>, kTraceBlock,
-                                                   persistent_stack_bytes(s, false)) != hipSuccess ||
-      nc <= 0)
+  const hipError_t e =
+      s.trace_ring ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nc, k_trace_closest<false>, kTraceBlock,
+                                                                  ring_stack_bytes(s))
+                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nc, k_trace_closest_refill<false>, kTraceBlock,
+                                                                  persistent_stack_bytes(s, false));
+  if (e != hipSuccess || nc <= 0)
     nc = 4;
   return nc;
 }

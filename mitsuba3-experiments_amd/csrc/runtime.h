@@ -113,6 +113,9 @@ struct Knobs {
   uint32_t urefill = 24;  // refill a wave once 24 lanes are idle (16: closest +1.3 %, 32: +2 %; 4-wide BVH)
   uint32_t cam_urefill = 64;  // k_trace_camera (MTX_CAM_UREFILL): whole waves refill; a refill derives its camera rays
   uint32_t occ_urefill = 12;  // any hit on the 8-wide tree (MTX_OCC_UREFILL; 8-16 alike, 24: shadow +1 ms, 32/40: +2/+3 ms)
+  // k_trace_closest: prepared rays per wave in LDS (MTX_TRACE_RING: 0 = none, urefill refills; 16; 32). The
+  // rings take their bytes from that kernel's LDS stack entries (wavefront.h split_trace_lds).
+  uint32_t trace_ring = MTX_TRACE_RING;
   uint32_t xcd_claim = 1;
   // ReSTIR GI: a band of at most this many paths runs its stage A in the
   // per-lane megakernel on one wavefront (MTX_MEGA_PATHS, 0 = off; default

@@ -200,6 +200,7 @@ int mtx_scene_upload(mtx_ctx *c, const mtx_scene_desc *d) {
   s.occ_stack_entries = occ_depth + 1;
   s.occ_lds_entries = std::min<uint32_t>(s.occ_stack_entries, c->knobs.occ_lds_stack);
   s.occ_lds_top = std::min<uint32_t>(n_occ, c->knobs.occ_lds_top);
+  mtxd::split_trace_lds(s, c->knobs.trace_ring);  // k_trace_closest: its rings' bytes come out of its stack entries
   s.trace_batch = c->knobs.trace_batch;
   s.urefill = c->knobs.urefill;
   s.cam_urefill = c->knobs.cam_urefill;

@@ -57,6 +57,19 @@ constexpr uint32_t kOccLdsStack = 8;
 #ifndef MTX_OCC_LDS_TOP
 #define MTX_OCC_LDS_TOP 48  // occlusion tree nodes copied into LDS per trace block (0 = none)
 #endif
+// Prepared-ray ring of k_trace_closest (device_common.h RayRing): each wave
+// of a block keeps up to R rays, set up and ready to start, in the block's
+// LDS behind the tree top. An entry is the TraceRay (13 words) and the queue
+// position; the ring's bytes come out of the 20 KB a trace block has (8
+// blocks per CU), so that kernel's stack keeps fewer entries in LDS.
+#ifndef MTX_TRACE_RING
+#define MTX_TRACE_RING 32  // R (MTX_TRACE_RING env: 0 = none, 16, 32)
+#endif
+constexpr bool ring_size_ok(long R) { return R == 0 || R == 16 || R == 32; }
+static_assert(ring_size_ok(MTX_TRACE_RING), "MTX_TRACE_RING: 0, 16 or 32");
+constexpr uint32_t kTraceLds = 20 * 1024;  // LDS of a trace block
+constexpr uint32_t kRingWords = 14;        // TraceRay | queue position
+constexpr uint32_t ring_bytes(uint32_t R) { return R * 4u * kRingWords * (kTraceBlock / 64u); }
 #ifndef MTX_CACHE_SORT
 #define MTX_CACHE_SORT 2  // NRC cache query order (render.cpp run_cache): 0 as appended, 1 Morton sort, 2 region x XCD
 #endif
@@ -106,6 +119,8 @@ struct DevScene {
   uint32_t urefill;        // persistent kernels: refill a wave once this many lanes are idle
   uint32_t cam_urefill;    // the same for k_trace_camera, whose refill derives the rays
   uint32_t occ_urefill;    // the same for the any-hit kernels
+  uint32_t trace_ring;     // k_trace_closest: prepared rays a wave keeps in LDS (0: none, urefill refills)
+  uint32_t ring_lds_entries, ring_lds_top;  // that kernel's lds_entries / lds_top beside its rings
   uint32_t xcd_claim;      // persistent kernels: claim rays from the own XCD's queue segment first
   mtx_camera camera;
   // constant environment (mtx_core/interaction.h SceneView: emitter index n_emitters)
@@ -113,11 +128,45 @@ struct DevScene {
   float env_radiance[3], env_center[3], env_radius;
 };
 
+// The persistent kernels keep only the top lds_entries entries in LDS (so
+// LDS does not cap occupancy) and spill deeper entries to a per-thread global
+// area ([entry - lds_entries][thread], coalesced per depth), rarely touched.
+// Behind the stack columns each block holds an LDS copy of the first lds_top
+// nodes of its tree (the top of the breadth-first tree).
+inline size_t persistent_stack_bytes(const DevScene &s, bool occ) {
+  return occ ? (size_t)s.occ_lds_entries * kTraceBlock * 8 + (size_t)s.occ_lds_top * 80
+             : (size_t)s.lds_entries * kTraceBlock * 4 + (size_t)s.lds_top * 64;
+}
+// k_trace_closest with rings of s.trace_ring rays: its view of the scene (the
+// LDS split of split_trace_lds) and its block's LDS, the rings behind the top.
+inline DevScene ring_view(const DevScene &s) {
+  DevScene v = s;
+  v.lds_entries = s.ring_lds_entries;
+  v.lds_top = s.ring_lds_top;
+  return v;
+}
+inline size_t ring_stack_bytes(const DevScene &s) {
+  return persistent_stack_bytes(ring_view(s), false) + ring_bytes(s.trace_ring);
+}
+// The split: a block with rings stays within kTraceLds. The rings displace
+// tree-top nodes only where one stack entry would not fit beside them, and
+// stack entries otherwise (deeper entries spill to the global area).
+inline void split_trace_lds(DevScene &s, uint32_t ring) {
+  s.trace_ring = ring;
+  s.ring_lds_entries = s.lds_entries;
+  s.ring_lds_top = s.lds_top;
+  if (!ring) return;
+  const uint32_t room = kTraceLds - ring_bytes(ring), entry = kTraceBlock * 4;
+  s.ring_lds_top = s.lds_top < (room - entry) / 64 ? s.lds_top : (room - entry) / 64;
+  const uint32_t fit = (room - s.ring_lds_top * 64) / entry;
+  if (s.ring_lds_entries > fit) s.ring_lds_entries = fit;
+}
+
 // Global spill area of a wavefront's traversals (the deeper of the two
 // trees' needs; closest-hit and any-hit launches of one wavefront never
 // overlap).
 inline size_t stack_ovf_bytes(const DevScene &s) {
-  const size_t a = (size_t)(s.stack_entries - s.lds_entries) * sizeof(int32_t);
+  const size_t a = (size_t)(s.stack_entries - s.ring_lds_entries) * sizeof(int32_t);  // <= lds_entries
   const size_t b = (size_t)(s.occ_stack_entries - s.occ_lds_entries) * sizeof(uint2);
   const size_t n = (a > b ? a : b) * s.ovf_threads;
   return n > 8 ? n : 8;
