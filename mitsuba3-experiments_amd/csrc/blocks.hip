@@ -260,7 +260,7 @@ __global__ __launch_bounds__(kBlkBlock) void k_blk_math(int op, uint32_t n, cons
   }
 }
 
-// sensor.sample_ray (path.py:45-62): camera_path's two lines (kernels.hip)
+// sensor.sample_ray (path.py:45-62): camera_path's two lines (camera_dev.h)
 // on a film position the caller holds.
 __global__ __launch_bounds__(kBlkBlock) void k_blk_sensor_ray(mtx_camera cam, uint32_t n, const float *pos,
                                                               const uint8_t *active, float *o, float *d,
@@ -697,48 +697,24 @@ void launch_blk_film_claim(const FilmBand &g, uint32_t n, const float *pos, cons
   hipLaunchKernelGGL(k_blk_film_claim, dim3(blk_grid(n, kBlkBlock)), dim3(kBlkBlock), 0, st, g, n, pos, active, s, px0,
                      counts);
 }
-template <int N, uint32_t F>
-static void launch_blk_film_put_t(const FilmBand &g, uint32_t n, const float *pos, const float *L,
-                                  const uint32_t *key_size, const uint32_t *key_offset, const uint32_t *order,
-                                  uint32_t spp_total, uint32_t sample_offset, float4 *planes, hipStream_t st) {
-  hipLaunchKernelGGL((k_blk_film_put<N, F>), dim3((g.band_px + 127) / 128), dim3(128), 0, st, g, n, pos, L, key_size,
-                     key_offset, order, spp_total, sample_offset, planes);
-}
 void launch_blk_film_put(const FilmBand &g, uint32_t n, const float *pos, const float *L, const uint32_t *key_size,
                          const uint32_t *key_offset, const uint32_t *order, uint32_t spp_total,
                          uint32_t sample_offset, float4 *planes, hipStream_t st) {
-  if (g.rfilter == MTX_RFILTER_BOX)
-    launch_blk_film_put_t<0, MTX_RFILTER_BOX>(g, n, pos, L, key_size, key_offset, order, spp_total, sample_offset,
-                                              planes, st);
-  else if (g.rfilter == MTX_RFILTER_GAUSSIAN)
-    launch_blk_film_put_t<2, MTX_RFILTER_GAUSSIAN>(g, n, pos, L, key_size, key_offset, order, spp_total,
-                                                   sample_offset, planes, st);
-  else
-    launch_blk_film_put_t<1, MTX_RFILTER_TENT>(g, n, pos, L, key_size, key_offset, order, spp_total, sample_offset,
-                                               planes, st);
-}
-template <int N, uint32_t F>
-static void launch_blk_film_put_staged_t(const FilmBand &g, uint32_t n, const float *pos, const float *L,
-                                         const uint8_t *active, uint32_t s, uint32_t px0, uint32_t spp_total,
-                                         uint32_t sample_offset, int ragged, float4 *planes, hipStream_t st) {
-  const uint32_t n_px = n / s;
-  // 5 planes x 64 rows of min(s, kPutStage) | 1 words: 3.8 KB at s = 3, 11.5 KB at 8 or 9, 21.8 KB from 16 on
-  const size_t lds = 5 * 64 * (size_t)(std::min<uint32_t>(s, kPutStage) | 1u) * sizeof(float);
-  hipLaunchKernelGGL((k_blk_film_put_staged<N, F>), dim3((n_px + 63) / 64), dim3(64), lds, st, g, n, pos, L, active, s,
-                     px0, n_px, spp_total, sample_offset, ragged, planes);
+  with_rfilter(g.rfilter, [&](auto N, auto F) {
+    hipLaunchKernelGGL((k_blk_film_put<decltype(N)::value, decltype(F)::value>), dim3((g.band_px + 127) / 128),
+                       dim3(128), 0, st, g, n, pos, L, key_size, key_offset, order, spp_total, sample_offset, planes);
+  });
 }
 void launch_blk_film_put_staged(const FilmBand &g, uint32_t n, const float *pos, const float *L,
                                 const uint8_t *active, uint32_t s, uint32_t px0, uint32_t spp_total,
                                 uint32_t sample_offset, int ragged, float4 *planes, hipStream_t st) {
-  if (g.rfilter == MTX_RFILTER_BOX)
-    launch_blk_film_put_staged_t<0, MTX_RFILTER_BOX>(g, n, pos, L, active, s, px0, spp_total, sample_offset, ragged,
-                                                     planes, st);
-  else if (g.rfilter == MTX_RFILTER_GAUSSIAN)
-    launch_blk_film_put_staged_t<2, MTX_RFILTER_GAUSSIAN>(g, n, pos, L, active, s, px0, spp_total, sample_offset,
-                                                          ragged, planes, st);
-  else
-    launch_blk_film_put_staged_t<1, MTX_RFILTER_TENT>(g, n, pos, L, active, s, px0, spp_total, sample_offset, ragged,
-                                                      planes, st);
+  const uint32_t n_px = n / s;
+  // 5 planes x 64 rows of min(s, kPutStage) | 1 words: 3.8 KB at s = 3, 11.5 KB at 8 or 9, 21.8 KB from 16 on
+  const size_t lds = 5 * 64 * (size_t)(std::min<uint32_t>(s, kPutStage) | 1u) * sizeof(float);
+  with_rfilter(g.rfilter, [&](auto N, auto F) {
+    hipLaunchKernelGGL((k_blk_film_put_staged<decltype(N)::value, decltype(F)::value>), dim3((n_px + 63) / 64),
+                       dim3(64), lds, st, g, n, pos, L, active, s, px0, n_px, spp_total, sample_offset, ragged, planes);
+  });
 }
 
 }  // namespace mtxd

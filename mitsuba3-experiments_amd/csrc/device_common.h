@@ -30,6 +30,21 @@ inline size_t stack_bytes(const DevScene &s) {
   return (a > b ? a : b) * sizeof(uint32_t) * kTraceBlock;
 }
 // The persistent kernels' LDS: wavefront.h persistent_stack_bytes.
+// Blocks of bs threads that cover n items (the per-item launchers).
+inline unsigned blocks_for(uint64_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
+
+// A sampler as it lies in a 16-B state record (misc, RestirBuffers::rng):
+// state lo | hi | seq | w, w the record's own word (depth | flags << 16).
+__device__ __forceinline__ Pcg32 ld_rng(uint4 m) {
+  Pcg32 g;
+  g.state = ((uint64_t)m.y << 32) | (uint64_t)m.x;
+  g.seq = m.z;
+  return g;
+}
+__device__ __forceinline__ uint4 st_rng(const Pcg32 &g, uint32_t w) {
+  return make_uint4((uint32_t)g.state, (uint32_t)(g.state >> 32), g.seq, w);
+}
+__device__ __forceinline__ float4 f4(V3 v, float w) { return make_float4(v.x, v.y, v.z, w); }
 
 __device__ __forceinline__ SceneView make_view(const DevScene &s) {
   SceneView v;

@@ -2,7 +2,7 @@
 // SURVEY §8f item 3): the left-hand side points (IntersectionSampler.sample,
 // nerad.py:291-310) and the right-hand side estimate (Integrator.sample_rhs,
 // nerad.py:174-233) on the wavefront. The RHS lanes (M per point, dr.repeat
-// at :182) run k_shade<MTX_INT_NERAD_RHS> (kernels.hip, shade_nerad) over
+// at :182) run k_shade<MTX_INT_NERAD_RHS> (shade.hip; shade_dev.h shade_nerad) over
 // the same persistent trace kernels as the path tracers; their stop
 // vertices query the fp16 MFMA field (field.hip) through the NRC cache
 // queue, then k_nerad_apply and k_nerad_mean form L_rhs.

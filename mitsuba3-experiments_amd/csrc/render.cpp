@@ -532,7 +532,7 @@ int render_restir(mtx_ctx *c, const mtx_render_args *a, float4 *film_dev, Timer 
     hipStream_t sh[2] = {st, wv[1].stream};
     if (mega_all && c->knobs.rs_fused) {
       // the whole stage A up to k_rs_collect in one per-lane launch
-      // (kernels.hip k_rs_stage_a), then the temporal pass
+      // (mega.hip k_rs_stage_a), then the temporal pass
       HIP_TRY(reset_counters(b, depth, st));
       e = tm.begin(0, st);
       mtxd::launch_rs_stage_a(sc[0], b, p, r,

@@ -5,7 +5,7 @@
 // other pixels' results of the previous phase, so each becomes one or more
 // kernels over all W*H*spp lanes:
 //
-//   raygen + trace_closest   primary rays (kernels.hip, bounce 0)
+//   raygen + trace_closest   primary rays (shade.hip / trace.hip, bounce 0)
 //   k_rs_begin               emittance, BSDF/hemisphere sample, secondary ray
 //   [trace, shade, shadow]*  the path-mis loop of sample_ray (:459-588) on the
 //                            wavefront machinery; shade bounce 0 records x_s,n_s

@@ -1,6 +1,6 @@
 // restir_dev.h — per-lane ReSTIR GI state loads / stores (the planes of
 // wavefront.h RestirBuffers), shared by restir.hip's phase kernels and the
-// stage-A path megakernel in kernels.hip.
+// stage-A path megakernel in mega.hip.
 #pragma once
 #include "device_common.h"
 #include "mtx_core/restir.h"
@@ -43,19 +43,5 @@ __device__ __forceinline__ void st_res(float4 *b, uint32_t n, uint32_t i, const 
   st_sample(b, n, i, r.z);
   b[5 * (size_t)n + i] = make_float4(r.w, r.W, __uint_as_float(r.M), 0.f);
 }
-
-__device__ __forceinline__ Pcg32 ld_rng(uint4 m) {
-  Pcg32 g;
-  g.state = ((uint64_t)m.y << 32) | (uint64_t)m.x;
-  g.seq = m.z;
-  return g;
-}
-
-__device__ __forceinline__ uint4 st_rng(const Pcg32 &g, uint32_t w) {
-  return make_uint4((uint32_t)g.state, (uint32_t)(g.state >> 32), g.seq, w);
-}
-
-__device__ __forceinline__ float4 f4(V3 v, float w) { return make_float4(v.x, v.y, v.z, w); }
-
 
 }  // namespace mtxd

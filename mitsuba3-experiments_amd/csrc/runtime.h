@@ -123,7 +123,7 @@ struct Knobs {
   // 2 x mega_grid x kShadeBlock)
   uint32_t mega_paths = 0xffffffffu;
   // such a band's whole stage A (raygen .. collect) in one per-lane launch
-  // (kernels.hip k_rs_stage_a; MTX_RS_FUSED=0: raygen, trace, k_rs_begin, the
+  // (mega.hip k_rs_stage_a; MTX_RS_FUSED=0: raygen, trace, k_rs_begin, the
   // megakernel and k_rs_collect as separate launches)
   uint32_t rs_fused = 1;
   // NRC cache query order: MTX_CACHE_SORT=1 Morton-sorted (host sync; measured slower), 2 grouped

@@ -173,10 +173,10 @@ inline size_t stack_ovf_bytes(const DevScene &s) {
 }
 
 // Shadow rays (WaveBuffers::shadow): four planes of `capacity` 16-B word
-// groups, o | d | t | x, record k at position k of each plane (kernels.hip
+// groups, o | d | t | x, record k at position k of each plane (shadow_dev.h
 // shadow_word): o.xyz maxt | d.xyz L index | t | x (L index = plane *
 // capacity + position of the path's L, WaveBuffers). Two forms, told apart
-// by flag bit 4 of t.w (kernels.hip make_shadow):
+// by flag bit 4 of t.w (shade_dev.h make_shadow):
 //   read-modify-write (the nerad integrators): t = T.xyz flags, x = X.xyz 0;
 //     flags bit0: fma form L = fma(T, X, L) (path-mis.py:117) else L = L + X
 //     (path.py:259, nrc.py:62); bits 1..3: the occluded-case contribution of
@@ -279,17 +279,17 @@ struct ChunkParams {
   uint32_t ident0;        // the bounce-0 queue is the identity (raygen): not stored, k_shade uses position = path
   uint32_t cam0;          // camera chunk without a stored raygen (needs ident0): the bounce-0 planes of ray_o /
                           // ray_d / misc and pos do not exist; the bounce-0 closest hit (k_trace_camera), the
-                          // bounce-0 shade and the film source kernels derive them (kernels.hip camera_path)
+                          // bounce-0 shade and the film source kernels derive them (camera_dev.h camera_path)
 };
 
-// -------- launch wrappers (kernels.hip) --------
+// -------- launch wrappers (trace.hip, shade.hip, mega.hip, film.hip) --------
 int trace_blocks_per_cu(const DevScene &s);    // any-hit kernels
 int closest_blocks_per_cu(const DevScene &s);  // k_trace_closest
 int shade_blocks_per_cu();
 int mega_blocks_per_cu(const DevScene &s);
 // all bounces of a short path-mis / path wavefront in one kernel (k_path_mega)
 void launch_path_mega(const DevScene &s, const WaveBuffers &b, const ChunkParams &p, int grid, hipStream_t st);
-// ReSTIR GI stage A of a short band (raygen .. collect) in one per-lane launch (kernels.hip)
+// ReSTIR GI stage A of a short band (raygen .. collect) in one per-lane launch (mega.hip)
 void launch_rs_stage_a(const DevScene &s, const WaveBuffers &b, const ChunkParams &p, const RestirBuffers &r,
                        int grid, hipStream_t st);
 int shade_stamps(unsigned long long *out);  // diagnostic builds (MTX_DIAG_STAMPS)
@@ -298,7 +298,7 @@ void launch_raygen_rays(const DevScene &s, const WaveBuffers &b, const ChunkPara
                         const uint32_t *lanes, uint32_t rng_skip, hipStream_t st);
 void launch_trace_closest(const DevScene &s, const WaveBuffers &b, uint32_t bounce, uint32_t stats, int grid,
                           hipStream_t st);
-// bounce-0 closest hit of a cam0 chunk: camera rays derived in the traversal (kernels.hip CameraSrc)
+// bounce-0 closest hit of a cam0 chunk: camera rays derived in the traversal (trace.hip CameraSrc)
 void launch_trace_camera(const DevScene &s, const WaveBuffers &b, const ChunkParams &p, int grid, hipStream_t st);
 void launch_trace_shadow(const DevScene &s, const WaveBuffers &b, uint32_t bounce, uint32_t stats, int grid,
                          hipStream_t st);

@@ -116,7 +116,7 @@ def test_roughplastic_tables():
 
 
 def test_shadow_record_form_is_checked():
-    """make_shadow<INT, FINAL> (kernels.hip) static_asserts that an
+    """make_shadow<INT, FINAL> (shade_dev.h) static_asserts that an
     integrator's shadow-record form matches where its L is stored
     (shadow_final_form): the round-5 nerad regression made at compile time.
     A final-value record for the nerad RHS (L by path, read-modify-write
@@ -129,7 +129,7 @@ def test_shadow_record_form_is_checked():
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = os.path.join(root, "mitsuba3-experiments_amd", "csrc", "kernels.hip")
+    src = os.path.join(root, "mitsuba3-experiments_amd", "csrc", "shade.hip")
     cmd = [hipcc, "--offload-arch=gfx950", "-std=c++17", "-I" + os.path.join(root, "include"), "-fsyntax-only", src]
     ok = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     assert ok.returncode == 0, ok.stderr[-2000:]

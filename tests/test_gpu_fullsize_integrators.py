@@ -117,7 +117,7 @@ print("CHILD OK")
 
 
 def test_restir_1080p_path_megakernel_bit_exact():
-    """The path megakernel (csrc/kernels.hip k_path_mega: every bounce of a
+    """The path megakernel (csrc/mega.hip k_path_mega: every bounce of a
     secondary path in one thread, waves claiming 64 paths at a time) forced
     on for the whole 1080p frame (MTX_MEGA_PATHS above its 2.07 M paths;
     by default it runs only short bands): films, samples and temporal

@@ -1,6 +1,6 @@
 """How much does the order of a bounce's rays change closest-hit traversal
 time? (ray-order experiment.) The wavefront keeps the
-raygen order: pixel-major, a pixel's samples contiguous (kernels.hip
+raygen order: pixel-major, a pixel's samples contiguous (shade.hip
 k_raygen_camera), so a wave's secondary rays start at one pixel's hit points
 and point in random cosine-weighted directions. This script traces the same
 rays in several orders through mtx_trace (k_trace_raw, closest hit) and prints

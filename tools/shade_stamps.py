@@ -2,7 +2,7 @@
 (path-mis, bedroom 1280x720, spp 256) with the MTX_DIAG_STAMPS library
 variant (`make -C mitsuba3-experiments_amd/csrc variant NAME=stamps
 DEFS=-DMTX_DIAG_STAMPS=1`) and prints each phase's share of the shade
-kernel's wave-cycles (s_memtime stamps summed per wave, kernels.hip).
+kernel's wave-cycles (s_memtime stamps summed per wave, shade.hip).
 The stamp build's own run time is not quoted: read the shares."""
 import ctypes as C
 import json
@@ -14,7 +14,7 @@ os.environ["MTX_LIB_VARIANT"] = os.environ.get("MTX_STAMPS_VARIANT", "stamps")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mitsuba3-experiments_amd"))
 
-# segment k ends at MTX_STAMP(.., k) of kernels.hip, in the order a step runs them
+# segment k ends at MTX_STAMP(.., k) of shade.hip / shade_dev.h, in the order a step runs them
 SEGS = ["loop top -> shade start (queue entry, prefetched hit)",
         "-> surface interaction (ray_d, thr, L, misc, shading record)",
         "-> material + texture colour (bsdf_at)",
