@@ -204,7 +204,8 @@ def bsdf_probe(scene, mat, wi, wo, uv, u):
 
 
 def warp(op, u):
-    ops = {"cosine_hemisphere": 0, "disk_concentric": 1, "disk": 2, "std_normal": 3, "uniform_hemisphere": 4}
+    ops = {"cosine_hemisphere": 0, "disk_concentric": 1, "disk": 2, "std_normal": 3, "uniform_hemisphere": 4,
+           "uniform_sphere": 5, "uniform_triangle": 6}
     u = np.ascontiguousarray(u, np.float32)
     out = np.zeros((len(u), 3), np.float32)
     L = lib()

@@ -1407,6 +1407,8 @@ int orc_bsdf_probe(const mtx_scene_desc *d, uint32_t mat, uint64_t n, const floa
   SceneView s = make_view(d);
   if (mat >= d->n_materials) return -1;
   const mtx_material &m = s.materials[mat];
+  // items are independent (the chi-square tests probe millions)
+#pragma omp parallel for schedule(static)
   for (uint64_t i = 0; i < n; ++i) {
     V3 a{wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]}, b{wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]};
     V2 t{uv[2 * i], uv[2 * i + 1]};
@@ -1588,7 +1590,8 @@ int orc_tex_probe(const mtx_scene_desc *d, uint32_t tex, uint64_t n, const float
 
 // Warps used by the integrators (upstream mitsuba/core/warp.h).
 // op: 0 cosine hemisphere (3), 1 uniform disk concentric (2), 2 uniform
-// disk (2), 3 std normal (2), 4 uniform hemisphere (3)
+// disk (2), 3 std normal (2), 4 uniform hemisphere (3), 5 uniform sphere (3),
+// 6 uniform triangle (2, mtx_core/discrete.h)
 int orc_warp(int op, const float *u, float *out, uint64_t n) {
   for (uint64_t i = 0; i < n; ++i) {
     V2 s{u[2 * i], u[2 * i + 1]};
@@ -1601,6 +1604,8 @@ int orc_warp(int op, const float *u, float *out, uint64_t n) {
       case 2: p = square_to_uniform_disk(s); v = V3{p.x, p.y, 0}; break;
       case 3: p = square_to_std_normal(s); v = V3{p.x, p.y, 0}; break;
       case 4: v = square_to_uniform_hemisphere(s); break;
+      case 5: v = square_to_uniform_sphere(s); break;
+      case 6: p = square_to_uniform_triangle(s); v = V3{p.x, p.y, 0}; break;
       default: return -1;
     }
     o[0] = v.x; o[1] = v.y; o[2] = v.z;
