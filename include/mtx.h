@@ -773,6 +773,53 @@ int mtx_blocks_film_put_dev(mtx_ctx *ctx, float *planes, uint32_t width, uint32_
  * the slots' fixed tree -- the layout and order of mtx_render's film. */
 int mtx_blocks_film_gather_dev(mtx_ctx *ctx, const float *planes, uint32_t width, uint32_t y0, uint32_t y1,
                                uint32_t rfilter, float *film);
+/* A built hash grid as a fixed-radius query reads it: the points p (3, n) it
+ * was built over, their scalar bounds (minimum and maximum over all three
+ * axes, as the build takes them), resolution and n_cells of the build, and
+ * its cell_size, cell_offset (n_cells each) and sample_idx (n). All device
+ * pointers. */
+typedef struct mtx_hashgrid_view {
+  const float *p;
+  uint64_t n;
+  float bbmin, bbmax;
+  uint32_t resolution, n_cells;
+  const uint32_t *cell_size, *cell_offset, *sample_idx;
+} mtx_hashgrid_view;
+/* A query whose cell box holds more cells than this does no walk and fails. */
+#define MTX_HG_MAX_QUERY_CELLS 4096u
+/* Photon gather: the fixed-radius query below (mtx_hashgrid_query_count_dev,
+ * same walk, same order, same cap) over a grid whose samples are photons,
+ * fused with the density estimate at m visible points. Photon j: the world
+ * direction d (3, n) towards where it came from, its weight beta (3, n) and
+ * the segments of its light path, depth (n). Visible point i: its position
+ * p (3, m) is the query; material (m, < 0 = the null BSDF), uv (2, m), wi
+ * (3, m, local), the shading and geometric normals sh_n, n (3, m) and the
+ * segments of its camera path, depth (m). */
+typedef struct mtx_photon_planes {
+  const float *d, *beta;
+  const int32_t *depth;
+} mtx_photon_planes;
+typedef struct mtx_visible_planes {
+  const float *p;
+  const int32_t *material;
+  const float *uv, *wi, *sh_n, *n;
+  const int32_t *depth;
+} mtx_visible_planes;
+/* Per neighbour of lane i, in walk order: skipped if depth_i + depth_j >
+ * max_depth; wo = to_local(frame(sh_n), d_j); val = bsdf_eval_pdf(material,
+ * uv, wi, wo), the function mtx_blocks_bsdf_dev evaluates (radiance mode,
+ * f |wo.n_s|); cg = dot(n, d_j); skipped unless cg wo.z > 0 (the particle
+ * tracer's light-leak mask for the photon's direction) and wi.z wo.z > 0 (the
+ * photon arrived on the side the point is seen from); contrib = (val *
+ * beta_j) / |cg| per component, one product and one correctly rounded
+ * division; sum = sum + contrib from +0. out_sum (3, m), out_count (m): the
+ * neighbours that contributed. Needs a scene. A material index past the
+ * scene's materials is handled as the null BSDF and reported (MTX_E_ARG)
+ * like mtx_blocks_bsdf_dev's; queries over the cell cap are reported like
+ * the query's. */
+int mtx_blocks_photon_gather_dev(mtx_ctx *ctx, const mtx_hashgrid_view *grid, const mtx_photon_planes *photons,
+                                 const mtx_visible_planes *points, uint64_t m, const float *radius,
+                                 uint32_t radius_stride, uint32_t max_depth, float *out_sum, uint32_t *out_count);
 
 /* --------------------------- film filters ------------------------- */
 /* Host-only: border (pixels on every side of the raw film) and radius of a
@@ -829,6 +876,32 @@ int mtx_group_by_u32(mtx_ctx *ctx, const uint32_t *keys, uint64_t n, uint32_t n_
  * returns after the results are complete. */
 int mtx_group_by_u32_dev(mtx_ctx *ctx, const uint32_t *keys, uint64_t n, uint32_t n_keys, uint32_t *key_size,
                          uint32_t *key_offset, uint32_t *order);
+/* mtx_hashgrid_view and MTX_HG_MAX_QUERY_CELLS: with the photon gather above. */
+/* Fixed-radius query: the samples of the grid within radius of each of the
+ * m points q (3, m). One lane per query walks the grid cells its sphere can
+ * touch, ascending in cz, then cy, then cx, and inside a grid cell the
+ * samples in ascending index; samples of other grid cells that share the
+ * hash cell are told apart by their own cell coordinates, so a sample is met
+ * once. The cell coordinate of a value is the build's, with a negative or NaN
+ * argument giving 0, the argument clamped to resolution, and 0 everywhere
+ * when bbmax - bbmin is not positive. Sample j is a neighbour iff, in fp32
+ * without contraction, (dx dx + dy dy) + dz dz <= r r with dx = p.x - q.x,
+ * ...; NaN in q or r, or r < 0, gives none. radius: one device float for all
+ * queries (radius_stride 0) or m of them (radius_stride 1). count (m)
+ * receives each query's number of neighbours. A query whose cell box holds
+ * more than MTX_HG_MAX_QUERY_CELLS cells is not walked: MTX_E_ARG with the
+ * number of such queries (build the grid with resolution ~ extent / (2 r));
+ * the context stays usable. Entries of cell_size, cell_offset and sample_idx
+ * that would lead past n are not followed. Complete on return. */
+int mtx_hashgrid_query_count_dev(mtx_ctx *ctx, const mtx_hashgrid_view *grid, const float *q, uint64_t m,
+                                 const float *radius, uint32_t radius_stride, uint32_t *count);
+/* The pairs of the query above in walk order: query i writes its neighbours
+ * to query_idx / sample_idx_out [offset[i], offset[i] + count[i]), offset the
+ * exclusive scan of count, total its sum (< 2^31); a pair that would land at
+ * or past total is not written. */
+int mtx_hashgrid_query_fill_dev(mtx_ctx *ctx, const mtx_hashgrid_view *grid, const float *q, uint64_t m,
+                                const float *radius, uint32_t radius_stride, const uint32_t *offset, uint64_t total,
+                                uint32_t *query_idx, uint32_t *sample_idx_out);
 
 /* --------------------------- radiance field ----------------------- */
 /* nerad.py:54-106 Field (hash-grid + SH encoding, fp16 MLP with LeakyReLU,

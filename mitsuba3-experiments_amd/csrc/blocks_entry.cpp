@@ -6,6 +6,7 @@
 
 #include "runtime.h"
 #include "blocks.h"
+#include "photon.h"
 #include "mtx_core/bdpt.h"
 #include "mtx_core/film.h"
 #include "mtx_core/interaction.h"
@@ -255,7 +256,39 @@ int mtx_blocks_sensor_direction_dev(mtx_ctx *c, uint64_t n, const float *p, cons
   return blk_end(c, fn, nullptr);
 }
 
-// The host twin of the two kernels above: the same per-lane functions over a
+int mtx_blocks_photon_gather_dev(mtx_ctx *c, const mtx_hashgrid_view *grid, const mtx_photon_planes *ph,
+                                 const mtx_visible_planes *vp, uint64_t m, const float *radius,
+                                 uint32_t radius_stride, uint32_t max_depth, float *out_sum, uint32_t *out_count) {
+  const char *fn = "mtx_blocks_photon_gather_dev";
+  int rc = blk_begin(c, fn, m, true, {grid, ph, vp, radius, out_sum, out_count});
+  if (rc || m == 0) return rc;
+  if (!ph->d || !ph->beta || !ph->depth || !vp->p || !vp->material || !vp->uv || !vp->wi || !vp->sh_n || !vp->n ||
+      !vp->depth || radius_stride > 1) {
+    mtx_set_error("%s: null plane or radius_stride > 1", fn);
+    return MTX_E_ARG;
+  }
+  mtxd::HgView g;
+  if ((rc = hashgrid_view_check(c, fn, grid, m, &g)) ||
+      (rc = need_device(c, fn, {ph->d, ph->beta, ph->depth, vp->p, vp->material, vp->uv, vp->wi, vp->sh_n, vp->n,
+                                vp->depth, radius, out_sum, out_count})) ||
+      (rc = dalloc(c->scratch.s6, 64)))
+    return rc;
+  HIP_TRY(hipMemsetAsync(c->scratch.s6.p, 0, 8, c->stream));
+  mtxd::launch_photon_gather(c->scene.dev, c->scene.n_materials, g, *ph, *vp, (uint32_t)m, radius, radius_stride,
+                             max_depth, out_sum, out_count, (uint32_t *)c->scratch.s6.p, c->stream);
+  HIP_TRY(hipGetLastError());
+  uint32_t bad[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(bad, c->scratch.s6.p, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (bad[0]) return hashgrid_cap_error(fn, bad[0]);
+  if (bad[1]) {
+    mtx_set_error("%s: %u lanes with a material index past the scene's materials (handled as invalid)", fn, bad[1]);
+    return MTX_E_ARG;
+  }
+  return MTX_OK;
+}
+
+// The host twin of the emitter-ray and sensor-direction kernels: the same per-lane functions over a
 // host scene description, one item after the other.
 int mtx_blocks_light_host(const mtx_scene_desc *d, int op, uint64_t n, const float *in, float *out) {
   const char *fn = "mtx_blocks_light_host";

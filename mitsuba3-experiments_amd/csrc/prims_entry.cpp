@@ -1,12 +1,46 @@
-// prims_entry.cpp — the reconstruction-filter queries and the five primitives
-// (prims.hip), host and device-pointer entries.
+// prims_entry.cpp — the reconstruction-filter queries, the five primitives
+// (prims.hip), host and device-pointer entries, and the hash grid's
+// fixed-radius query (photon.hip), device pointers only.
 #include <algorithm>
 
 #include "runtime.h"
 #include "mtx_core/film.h"
+#include "photon.h"
 #include "prims.h"
 
 using namespace mtxh;
+
+// The fixed-radius query (photon.hip): the grid view's checks, shared with
+// the photon gather (blocks_entry.cpp), then count or fill.
+int mtxh::hashgrid_view_check(mtx_ctx *c, const char *fn, const mtx_hashgrid_view *g, uint64_t m, mtxd::HgView *out) {
+  if (!g || !g->p || !g->cell_size || !g->cell_offset || !g->sample_idx) {
+    mtx_set_error("%s: null grid argument", fn);
+    return MTX_E_ARG;
+  }
+  if (g->n == 0 || g->n >= (1ull << 31) || m >= (1ull << 31)) {
+    mtx_set_error("%s: the grid's n (%llu) and m (%llu) must be < 2^31, n > 0", fn, (unsigned long long)g->n,
+                  (unsigned long long)m);
+    return MTX_E_ARG;
+  }
+  if (g->n_cells == 0 || g->resolution == 0 || g->resolution > (1u << 24)) {
+    mtx_set_error("%s: n_cells %u / resolution %u (n_cells > 0, 0 < resolution <= 2^24)", fn, g->n_cells,
+                  g->resolution);
+    return MTX_E_ARG;
+  }
+  if (!(g->bbmin <= g->bbmax)) {
+    mtx_set_error("%s: bounds [%g, %g]", fn, g->bbmin, g->bbmax);
+    return MTX_E_ARG;
+  }
+  if (int rc = need_device(c, fn, {g->p, g->cell_size, g->cell_offset, g->sample_idx})) return rc;
+  *out = mtxd::HgView{g->p, (uint32_t)g->n, g->bbmin, g->bbmax, g->resolution, g->n_cells, g->cell_size,
+                      g->cell_offset, g->sample_idx};
+  return MTX_OK;
+}
+int mtxh::hashgrid_cap_error(const char *fn, uint32_t bad) {
+  mtx_set_error("%s: %u queries whose cell box holds more than %u cells (not walked); build the grid with "
+                "resolution ~ extent / (2 r)", fn, bad, MTX_HG_MAX_QUERY_CELLS);
+  return MTX_E_ARG;
+}
 
 extern "C" {
 
@@ -224,6 +258,45 @@ static int scatter_reduce_f32_impl(mtx_ctx *c, const char *fn, bool dev, int op,
   return dev ? MTX_OK : unstage(c, {{target, c->scratch.s0, 4 * n_target}});
 }
 
+static int hashgrid_query_impl(mtx_ctx *c, const char *fn, bool fill, const mtx_hashgrid_view *grid, const float *q,
+                               uint64_t m, const float *radius, uint32_t radius_stride, uint32_t *count,
+                               const uint32_t *offset, uint64_t total, uint32_t *query_idx, uint32_t *sample_idx_out) {
+  if (!c) {
+    mtx_set_error("%s: null context", fn);
+    return MTX_E_ARG;
+  }
+  if (m == 0) return MTX_OK;
+  if (!q || !radius || radius_stride > 1 || (fill ? !offset || (total && (!query_idx || !sample_idx_out)) : !count)) {
+    mtx_set_error("%s: null argument or radius_stride > 1", fn);
+    return MTX_E_ARG;
+  }
+  if (total >= (1ull << 31)) {
+    mtx_set_error("%s: total >= 2^31", fn);
+    return MTX_E_ARG;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  mtxd::HgView g;
+  if ((rc = hashgrid_view_check(c, fn, grid, m, &g)) ||
+      (rc = need_device(c, fn, {q, radius, count, offset, query_idx, sample_idx_out})))
+    return rc;
+  if ((rc = dalloc(c->scratch.s6, 64))) return rc;
+  HIP_TRY(hipMemsetAsync(c->scratch.s6.p, 0, 4, c->stream));
+  uint32_t *d_bad = (uint32_t *)c->scratch.s6.p;
+  if ((rc = prim_run(c, [&] {
+         if (fill)
+           mtxd::launch_hg_fill(g, (uint32_t)m, q, radius, radius_stride, offset, (uint32_t)total, query_idx,
+                                sample_idx_out, d_bad, c->stream);
+         else
+           mtxd::launch_hg_count(g, (uint32_t)m, q, radius, radius_stride, count, d_bad, c->stream);
+         return MTX_OK;
+       })))
+    return rc;
+  uint32_t bad = 0;
+  HIP_TRY(hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost));
+  return bad ? hashgrid_cap_error(fn, bad) : MTX_OK;
+}
+
 int mtx_prefix_sum_u32(mtx_ctx *c, const uint32_t *in, uint32_t *out, uint64_t n, int inclusive) {
   return prefix_sum_u32_impl(c, "mtx_prefix_sum_u32", false, in, out, n, inclusive);
 }
@@ -265,6 +338,18 @@ int mtx_scatter_reduce_f32(mtx_ctx *c, int op, float *target, uint64_t n_target,
 int mtx_scatter_reduce_f32_dev(mtx_ctx *c, int op, float *target, uint64_t n_target, const float *value,
                                const uint32_t *index, uint64_t n_value) {
   return scatter_reduce_f32_impl(c, "mtx_scatter_reduce_f32_dev", true, op, target, n_target, value, index, n_value);
+}
+
+int mtx_hashgrid_query_count_dev(mtx_ctx *c, const mtx_hashgrid_view *grid, const float *q, uint64_t m,
+                                 const float *radius, uint32_t radius_stride, uint32_t *count) {
+  return hashgrid_query_impl(c, "mtx_hashgrid_query_count_dev", false, grid, q, m, radius, radius_stride, count,
+                             nullptr, 0, nullptr, nullptr);
+}
+int mtx_hashgrid_query_fill_dev(mtx_ctx *c, const mtx_hashgrid_view *grid, const float *q, uint64_t m,
+                                const float *radius, uint32_t radius_stride, const uint32_t *offset, uint64_t total,
+                                uint32_t *query_idx, uint32_t *sample_idx_out) {
+  return hashgrid_query_impl(c, "mtx_hashgrid_query_fill_dev", true, grid, q, m, radius, radius_stride, nullptr,
+                             offset, total, query_idx, sample_idx_out);
 }
 
 }  // extern "C"

@@ -326,6 +326,23 @@ class PathPlanes(C.Structure):
         "len", "p", "n", "sh_n", "wi", "uv", "material", "emitter", "beta", "pdf_fwd", "pdf_rev", "delta")]
 
 
+class HashGridView(C.Structure):
+    """mtx_hashgrid_view: a built hash grid as the fixed-radius query reads it."""
+    _fields_ = [("p", C.c_void_p), ("n", C.c_uint64), ("bbmin", C.c_float), ("bbmax", C.c_float),
+                ("resolution", C.c_uint32), ("n_cells", C.c_uint32), ("cell_size", C.c_void_p),
+                ("cell_offset", C.c_void_p), ("sample_idx", C.c_void_p)]
+
+
+class PhotonPlanes(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("d", "beta", "depth")]
+
+
+class VisiblePlanes(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("p", "material", "uv", "wi", "sh_n", "n", "depth")]
+
+
+MTX_HG_MAX_QUERY_CELLS = 4096
+
 MTX_MATH_FMA, MTX_MATH_DIV, MTX_MATH_RCP, MTX_MATH_SQRT, MTX_MATH_DOT3 = 0, 1, 2, 3, 4
 MTX_MATH_NORM3, MTX_MATH_NORMALIZE3, MTX_MATH_TO_LOCAL, MTX_MATH_TO_WORLD = 5, 6, 7, 8
 MTX_MATH_MIS_A, MTX_MATH_MIS_B = 9, 10
@@ -398,4 +415,7 @@ EXPORTS = [
     "mtx_blocks_bdpt_host",
     "mtx_blocks_film_put_dev",
     "mtx_blocks_film_gather_dev",
+    "mtx_hashgrid_query_count_dev",
+    "mtx_hashgrid_query_fill_dev",
+    "mtx_blocks_photon_gather_dev",
 ]

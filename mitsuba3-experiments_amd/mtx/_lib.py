@@ -115,6 +115,10 @@ def lib() -> C.CDLL:
         "mtx_blocks_film_put_dev": ([vp, vp, u32, u32, u32, u32, u64, vp, vp, vp, u32, u32, u32, u32, C.POINTER(u64)],
                                     C.c_int),
         "mtx_blocks_film_gather_dev": ([vp, vp, u32, u32, u32, u32, vp], C.c_int),
+        "mtx_hashgrid_query_count_dev": ([vp, C.POINTER(_abi.HashGridView), vp, u64, vp, u32, vp], C.c_int),
+        "mtx_hashgrid_query_fill_dev": ([vp, C.POINTER(_abi.HashGridView), vp, u64, vp, u32, vp, u64, vp, vp], C.c_int),
+        "mtx_blocks_photon_gather_dev": ([vp, C.POINTER(_abi.HashGridView), C.POINTER(_abi.PhotonPlanes),
+                                          C.POINTER(_abi.VisiblePlanes), u64, vp, u32, u32, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -39,6 +39,12 @@ The two meet in :class:`PathVertices` (a vertex store per subpath),
 :func:`connect_subpaths` (every connection strategy (s, t) with its shadow
 ray and its power-heuristic weight, one kernel; include/mtx_core/bdpt.h) and
 :class:`BidirectionalPathTracer` (``"bdpt"``).
+
+Photons: ``mtx.primitives.HashGrid.query`` finds the samples within a radius
+of each query point in a fixed walk order, :meth:`Scene.photon_gather` fuses
+that walk with the density estimate at visible points (one kernel, equal to
+its composition from the blocks bit for bit) and :class:`PhotonMapper`
+(``"sppm"``) is the progressive photon mapper built on them.
 """
 from __future__ import annotations
 
@@ -526,6 +532,58 @@ class Scene:
             check(lib().mtx_blocks_bsdf_dev(self._call(dev), n, si.material.data_ptr(), None, None, None, None, None,
                                             None, None, out.data_ptr()), "mtx_blocks_bsdf_dev")
         return out
+
+    # ------------------------------------------------------------ photons --
+    def photon_gather(self, grid, si, depth_q, radius, d_p, beta_p, depth_p, max_depth):
+        """The density estimate at the visible points `si` over the photons
+        of `grid` (a ``mtx.primitives.HashGrid`` built over their positions)
+        within `radius` (a float or an (N,) tensor), one fused kernel:
+        ``grid.query`` 's walk, and per neighbour j of lane i, in walk order,
+        ``depth_q[i] + depth_p[j] <= max_depth``; wo = to_local(si.sh_n, d_p[j]);
+        val = bsdf.eval(si, wo) (with its shading cosine, as
+        :meth:`bsdf_eval_pdf_sample` returns it); cg = dot(si.n, d_p[j]); the
+        pair counts where cg * wo.z > 0 and si.wi.z * wo.z > 0; sum += val *
+        beta_p[j] / |cg|. Returns (sum (3, N), count (N, int32): the pairs
+        that counted). d_p, beta_p (3, n): each photon's world direction
+        towards where it came from and its weight; depth_p (n, int32),
+        depth_q (an int or (N,) int32): segments of the two subpaths.
+        si.material < 0: the null BSDF, nothing is gathered. Needs si.p,
+        material, uv, wi, sh_n and n. The result equals the composition
+        query / index_select / to_local / bsdf_eval_pdf_sample / dot / div /
+        scatter_reduce_with("add") bit for bit."""
+        torch = _torch()
+        name = "photon_gather"
+        if not hasattr(grid, "_query_args"):
+            raise MtxError(f"{name}: grid: expected a mtx.primitives.HashGrid")
+        m = _f32(f"{name}: si.p", si.p, 3, None)
+        dev = si.p.device
+        _, rad, stride = grid._query_args(si.p, radius, name)
+        _i32(f"{name}: si.material", si.material, m, dev)
+        _f32(f"{name}: si.uv", si.uv, 2, m, dev)
+        _f32(f"{name}: si.wi", si.wi, 3, m, dev)
+        _f32(f"{name}: si.sh_n", si.sh_n, 3, m, dev)
+        _f32(f"{name}: si.n", si.n, 3, m, dev)
+        if isinstance(depth_q, torch.Tensor):
+            _i32(f"{name}: depth_q", depth_q, m, dev)
+        else:
+            depth_q = torch.full((m,), int(depth_q), dtype=torch.int32, device=dev)
+        n = grid.n_samples
+        _f32(f"{name}: d_p", d_p, 3, n, dev)
+        _f32(f"{name}: beta_p", beta_p, 3, n, dev)
+        _i32(f"{name}: depth_p", depth_p, n, dev)
+        max_depth = int(max_depth)
+        if not 0 <= max_depth < 2 ** 32:
+            raise MtxError(f"{name}: max_depth = {max_depth}: expected a segment count in [0, 2^32)")
+        out, cnt = torch.zeros((3, m), dtype=torch.float32, device=dev), torch.zeros(m, dtype=torch.int32, device=dev)
+        if m and n:
+            view = grid._view()
+            ph = _abi.PhotonPlanes(d_p.data_ptr(), beta_p.data_ptr(), depth_p.data_ptr())
+            vp = _abi.VisiblePlanes(si.p.data_ptr(), si.material.data_ptr(), si.uv.data_ptr(), si.wi.data_ptr(),
+                                    si.sh_n.data_ptr(), si.n.data_ptr(), depth_q.data_ptr())
+            check(lib().mtx_blocks_photon_gather_dev(self._call(dev), C.byref(view), C.byref(ph), C.byref(vp), m,
+                                                     rad.data_ptr(), stride, max_depth, out.data_ptr(),
+                                                     cnt.data_ptr()), "mtx_blocks_photon_gather_dev")
+        return out, cnt
 
 
 # ------------------------------------------------------------------ sensor --
@@ -1028,6 +1086,235 @@ class ParticleTracer(AdjointIntegrator):
                 inv_q = rcp(torch.where(alive, q, torch.ones_like(q)))
                 throughput, rel = throughput * inv_q, rel * inv_q
             o, d, maxt = si.spawn_ray(wo_w)
+
+
+# ---------------------------------------------------------- photon mapping --
+
+class _Visible:
+    """The planes :meth:`Scene.photon_gather` reads from an interaction."""
+
+    def __init__(self, si, material):
+        self.p, self.material, self.uv, self.wi, self.sh_n, self.n = si.p, material, si.uv, si.wi, si.sh_n, si.n
+
+
+class PhotonMapper(SamplingIntegrator):
+    """Progressive photon mapping on the blocks (``"sppm"``): what the
+    reference's sppm.py set out to do, finished in the other direction. The
+    grid holds the photons of a pass and the visible points query it, so every
+    pixel sums its photons in the walk's fixed order and the film is
+    deterministic; the reference's grid held visible points, and scattering
+    photons into them is race-ordered.
+
+    Properties: ``max_depth`` (-1 = unbounded), ``rr_depth`` (5),
+    ``hide_emitters`` (False): as ``ptracer``, counting segments;
+    ``photons_per_pass`` (the film's pixel count); ``initial_radius`` (the
+    radius of the scene's bounding sphere / 200); ``alpha`` (2 / 3);
+    ``rfilter``.
+
+    ``render(scene, sensor, seed, spp)`` runs spp passes. Pass i gathers with
+    r_i, r_i^2 = r_0^2 prod_{k=1..i} (k - 1 + alpha) / k: the global radius
+    schedule of Knaus and Zwicker's probabilistic formulation, the limit of
+    SPPM's per-pixel statistics with no per-pixel state (float64 on the host,
+    rounded once).
+
+    Photon stage: the light walk of :class:`ParticleTracer` (emission,
+    ``ray_intersect``, the BSDF sample with the adjoint correction and the
+    eta^2 undo, Russian roulette) without the sensor connections; every hit
+    on a material with a smooth lobe deposits (p, the direction back along the
+    path, the throughput, the segments so far). One
+    ``mtx.primitives.HashGrid`` over the deposits, resolution =
+    clamp(floor(extent / (2 r_i)), 1, 1024).
+
+    Camera stage: one jittered sample per pixel, sample i of spp in the film.
+    At every vertex the emitted radiance counts where ``ptracer`` counts it
+    (seen directly, or through a chain of delta lobes); a material with a
+    smooth lobe adds throughput * sum / (pi r_i^2 photons_per_pass) from one
+    :meth:`Scene.photon_gather`; then the BSDF sample is drawn and the path
+    continues only where the sampled lobe is a delta or null lobe, with its
+    weight (sppm.py:226 follows the sampled non-smooth lobe): the gather
+    accounts for the smooth part in full, so a material with both is
+    estimated without bias in the lobe choice. sppm.py:207's fixed depth 6 is
+    ``max_depth``. The film depends on seed, spp, photons_per_pass and the
+    properties alone."""
+
+    name = "sppm"
+
+    def __init__(self, props=None):
+        super().__init__(props)
+        self.max_depth = int(self.props.get("max_depth", -1))
+        self.rr_depth = int(self.props.get("rr_depth", 5))
+        self.hide_emitters = bool(self.props.get("hide_emitters", False))
+        ppp, r0 = self.props.get("photons_per_pass", None), self.props.get("initial_radius", None)
+        self.photons_per_pass = None if ppp is None else int(ppp)
+        self.initial_radius = None if r0 is None else float(r0)
+        self.alpha = float(self.props.get("alpha", 2.0 / 3.0))
+        if self.max_depth < -1:
+            raise MtxError(f"max_depth = {self.max_depth}: expected -1 (unbounded) or a segment count >= 0")
+        if self.photons_per_pass is not None and self.photons_per_pass <= 0:
+            raise MtxError(f"photons_per_pass = {self.photons_per_pass}: expected a positive photon count")
+        if self.initial_radius is not None and not self.initial_radius > 0:
+            raise MtxError(f"initial_radius = {self.initial_radius}: expected a positive radius")
+        if not 0 < self.alpha <= 1:
+            raise MtxError(f"alpha = {self.alpha}: expected 0 < alpha <= 1")
+
+    def check_scene(self, scene) -> None:
+        for i, m in enumerate(scene.scene.materials):
+            if m.type == _abi.MTX_MAT_ROUGHDIELECTRIC:
+                raise MtxError(f"sppm: material {i} is a roughdielectric: a light path through it needs the adjoint "
+                               "of its BSDF (its eta), which the blocks evaluate in radiance mode only")
+
+    def radius(self, i: int, r0: float) -> float:
+        """r_i of pass i (0-based) as the float32 the kernels use."""
+        r2 = float(r0) ** 2
+        for k in range(1, int(i) + 1):
+            r2 *= (k - 1 + self.alpha) / k
+        return float(np.float32(np.sqrt(r2)))
+
+    @staticmethod
+    def _default_radius(scene) -> float:
+        v = np.asarray(scene.scene.vpos, np.float64).reshape(-1, 3)
+        return float(0.5 * np.linalg.norm(v.max(0) - v.min(0)) / 200.0)
+
+    def trace_photons(self, scene, sampler, max_depth):
+        """One light walk of sampler.n photons -> (p, d_p, beta_p (3, n),
+        depth_p (n, int32)): the deposits, compacted in (bounce, lane) order."""
+        torch = _torch()
+        n, dev = sampler.n, sampler.device
+        ray, weight, es = scene.sample_emitter_ray(sampler.next_2d(), sampler.next_2d())
+        alive = es.emitter >= 0
+        throughput, rel = weight, torch.ones((3, n), device=dev)
+        eta = torch.ones(n, device=dev)
+        o, d, maxt = ray.o, ray.d, ray.maxt
+        P, D, B, K = [], [], [], []
+        k = 1  # segments of the ray being traced; a visible point adds at least one
+        while k + 1 <= max_depth and bool(alive.any()):
+            si = scene.ray_intersect(o, d, maxt, alive)
+            alive = alive & si.valid
+            wi_w = si.to_world(si.wi)
+            wi_g = dot(si.n, wi_w)
+            keep = alive & ((scene.bsdf_flags(si) & BF_SMOOTH) != 0)
+            P.append(si.p[:, keep])
+            D.append(wi_w[:, keep])
+            B.append(throughput[:, keep])
+            K.append(torch.full((int(keep.sum().item()),), k, dtype=torch.int32, device=dev))
+            k += 1
+            if k + 1 > max_depth:
+                break
+            s1, s2 = sampler.next_1d(), sampler.next_2d()
+            _val, _pdf, bs, bw = scene.bsdf_eval_pdf_sample(si, si.wi, s1, s2, alive)
+            wo_w = si.to_world(bs.wo)
+            ok, corr = ParticleTracer._adjoint(si, wi_g, bs.wo, wo_w)
+            transmitted = (bs.sampled_type & 0x40) != 0  # BF_DELTA_TRANSMISSION: undo the radiance scale eta_ti^2
+            bw = torch.where(transmitted, bw * (bs.eta * bs.eta), bw) * corr
+            throughput, rel = throughput * bw, rel * bw
+            eta = eta * bs.eta
+            fmax = torch.fmax(torch.fmax(rel[0], rel[1]), rel[2])
+            alive = alive & ok & (fmax > 0)
+            if k >= self.rr_depth:
+                q = torch.fmin(fmax * (eta * eta), fmax.new_tensor(0.95))
+                alive = alive & (sampler.next_1d() < q)
+                inv_q = rcp(torch.where(alive, q, torch.ones_like(q)))
+                throughput, rel = throughput * inv_q, rel * inv_q
+            o, d, maxt = si.spawn_ray(wo_w)
+        if not P:
+            z = torch.zeros((3, 0), device=dev)
+            return z, z.clone(), z.clone(), torch.zeros(0, dtype=torch.int32, device=dev)
+        return (torch.cat(P, 1).contiguous(), torch.cat(D, 1).contiguous(), torch.cat(B, 1).contiguous(),
+                torch.cat(K).contiguous())
+
+    def build_grid(self, p, radius):
+        """The pass's hash grid over the deposit positions p (3, n), n > 0."""
+        from .primitives import HashGrid
+
+        torch = _torch()
+        ext = float((torch.amax(p) - torch.amin(p)).item())
+        res = int(min(max(np.floor(ext / (2.0 * radius)) if radius > 0 else 1, 1), 1024))
+        return HashGrid(p, res)
+
+    def gather_pass(self, scene, sampler, ray, grid, photons, radius, n_photons, max_depth):
+        """The camera stage of one pass -> L (3, N)."""
+        torch = _torch()
+        n, dev = sampler.n, sampler.device
+        L = torch.zeros((3, n), device=dev)
+        thr = torch.ones((3, n), device=dev)
+        active = torch.ones(n, dtype=torch.bool, device=dev)
+        o, d, maxt = ray.o, ray.d, ray.maxt
+        scale = float(1.0 / (np.pi * float(radius) ** 2 * float(n_photons)))
+        depth = 1  # segments of the camera path once this ray has hit
+        while depth <= max_depth and bool(active.any()):
+            si = scene.ray_intersect(o, d, maxt, active)
+            if depth > 1 or not self.hide_emitters:
+                L = L + thr * scene.emitter_eval(si, active)
+            active = active & si.valid
+            if depth + 1 > max_depth:
+                break
+            smooth = active & ((scene.bsdf_flags(si) & BF_SMOOTH) != 0)
+            if grid is not None and bool(smooth.any()):
+                vis = _Visible(si, torch.where(smooth, si.material, torch.full_like(si.material, -1)))
+                total, _cnt = scene.photon_gather(grid, vis, depth, radius, photons[0], photons[1], photons[2],
+                                                  max_depth)
+                L = L + thr * total * scale
+            s1, s2 = sampler.next_1d(), sampler.next_2d()
+            _val, _pdf, bs, bw = scene.bsdf_eval_pdf_sample(si, si.wi, s1, s2, active)
+            fmax = torch.fmax(torch.fmax(bw[0], bw[1]), bw[2])
+            active = active & ((bs.sampled_type & BF_DELTA) != 0) & (fmax > 0)
+            thr = thr * bw
+            depth += 1
+            if depth >= self.rr_depth:
+                tmax = torch.fmax(torch.fmax(thr[0], thr[1]), thr[2])
+                q = torch.fmin(tmax, tmax.new_tensor(0.95))
+                active = active & (sampler.next_1d() < q)
+                thr = thr * rcp(torch.where(active, q, torch.ones_like(q)))
+            o, d, maxt = si.spawn_ray(si.to_world(bs.wo))
+        return L
+
+    def render_film(self, scene, seed: int = 0, spp: int = 1, sensor=None, rfilter=None):
+        """The raw film tensor (H + 2b, W + 2b, 4) after spp passes."""
+        torch = _torch()
+        fid = self.rfilter_id(scene, rfilter)
+        sens = Sensor(scene, sensor)
+        scn = Scene(sens.scene, sens.ctx.device)
+        self.check_scene(scn)
+        W, H = sens.width, sens.height
+        spp = int(spp)
+        n_px = W * H
+        n_ph = n_px if self.photons_per_pass is None else self.photons_per_pass
+        if spp <= 0 or spp * max(n_px, n_ph) >= 2 ** 32:
+            raise MtxError("render_film: spp > 0 and spp * max(pixels, photons_per_pass) < 2^32 expected")
+        r0 = self._default_radius(scn) if self.initial_radius is None else self.initial_radius
+        max_depth = 2 ** 31 - 1 if self.max_depth < 0 else self.max_depth
+        film = Film(W, 0, H, fid, sens.ctx.device)
+        dev = film.device
+
+        def lanes_of(a):
+            a = a & 0xffffffff
+            return torch.where(a >= 2 ** 31, a - 2 ** 32, a).to(torch.int32)  # uint32 bit patterns
+
+        pix = torch.arange(n_px, dtype=torch.int64, device=dev)
+        px, py = (pix % W).to(torch.float32), (pix // W).to(torch.float32)
+        for i in range(spp):
+            r = self.radius(i, r0)
+            grid, photons = None, None
+            if max_depth >= 2:
+                ids = torch.arange(i * n_ph, (i + 1) * n_ph, dtype=torch.int64, device=dev)
+                # the photons' streams: another seed than the camera samples' (lane ids overlap)
+                p, d_p, beta_p, depth_p = self.trace_photons(scn, Sampler((int(seed) + 0x9e3779b9) & 0xffffffff,
+                                                                          lanes_of(ids)), max_depth)
+                if p.shape[1]:
+                    grid, photons = self.build_grid(p, r), (d_p, beta_p, depth_p)
+            sampler = Sampler(seed, lanes_of(pix * spp + i))
+            u = sampler.next_2d()  # the film jitter
+            pos = torch.stack([px + u[0], py + u[1]])
+            L = self.gather_pass(scn, sampler, sens.sample_ray(pos), grid, photons, r, n_ph, max_depth)
+            film.put(pos, L.contiguous(), spp_total=spp, sample_offset=i, pixel_major_spp=1, px0=0)
+        return film.raw()
+
+    def render(self, scene, sensor=None, seed: int = 0, spp: int = 1, develop: bool = True, rfilter=None):
+        """The (H, W, 3) image tensor, or the raw film with develop=False."""
+        raw = self.render_film(scene, seed=seed, spp=spp, sensor=sensor, rfilter=rfilter)
+        if not develop:
+            return raw
+        return globals()["develop"](raw, _abi.RFILTER_BORDER[self.rfilter_id(scene, rfilter)])
 
 
 # ------------------------------------------------- bidirectional connections --

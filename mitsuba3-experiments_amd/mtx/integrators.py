@@ -544,10 +544,11 @@ register_integrator("nerad", lambda props: NeradIntegrator(props))
 
 
 def _register_blocks_integrators() -> None:
-    from .blocks import BidirectionalPathTracer, ParticleTracer
+    from .blocks import BidirectionalPathTracer, ParticleTracer, PhotonMapper
 
     register_integrator("ptracer", ParticleTracer)  # testpssmlt.py:22-27; written on mtx.blocks
     register_integrator("bdpt", BidirectionalPathTracer)  # bdpt02.py's dictionary; finished, on mtx.blocks
+    register_integrator("sppm", PhotonMapper)  # sppm.py's integrator; finished, on mtx.blocks
 
 
 _register_blocks_integrators()

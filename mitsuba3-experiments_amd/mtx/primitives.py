@@ -77,7 +77,10 @@ class HashGrid:
     (Point3f as a [3, n] array). Attributes: cell_size, cell_offset (exclusive
     scan), sample_idx (samples grouped by cell, ascending sample index within
     a cell: one of the orders the reference's race-defined election can
-    produce, and a deterministic one), cell (per-sample cell index)."""
+    produce, and a deterministic one), cell (per-sample cell index). It keeps
+    the points (``points``) and knows its scalar bounds (``bbmin``, ``bbmax``,
+    computed on first use); a grid built over a torch CUDA tensor answers
+    fixed-radius queries (:meth:`query`)."""
 
     def __init__(self, sample, resolution: int, n_cells: int | None = None, device: int | None = None):
         if _torch_cuda(sample):  # a [3, n] float32 tensor in HBM: mtx_hashgrid_build_dev, int32 results there
@@ -85,6 +88,7 @@ class HashGrid:
 
             p = sample.to(torch.float32).reshape(3, -1).contiguous()
             n = p.shape[1]
+            self.points = p  # the (3, n) points: query() reads them
             self.n_samples, self.resolution = n, int(resolution)
             self.n_cells = int(n_cells if n_cells is not None else n)
             kw = {"dtype": torch.int32, "device": p.device}
@@ -98,6 +102,7 @@ class HashGrid:
             return
         p = np.ascontiguousarray(np.asarray(sample, np.float32).reshape(3, -1))
         n = p.shape[1]
+        self.points = p
         self.n_samples = n
         self.n_cells = int(n_cells if n_cells is not None else n)
         self.resolution = int(resolution)
@@ -110,6 +115,105 @@ class HashGrid:
                                        self.cell.ctypes.data, self.cell_size.ctypes.data,
                                        self.cell_offset.ctypes.data, self.sample_idx.ctypes.data),
               "mtx_hashgrid_build")
+
+    def _bounds(self):
+        if getattr(self, "_bb", None) is None:
+            p = self.points
+            if _torch_cuda(p):
+                import torch
+
+                self._bb = (float(torch.amin(p).item()), float(torch.amax(p).item())) if p.numel() else (0.0, 0.0)
+            else:
+                self._bb = (float(p.min()), float(p.max())) if p.size else (0.0, 0.0)
+        return self._bb
+
+    @property
+    def bbmin(self) -> float:
+        """The build's scalar lower bound: the minimum over all three axes
+        (min and max do not round, so this is the float the build used)."""
+        return self._bounds()[0]
+
+    @property
+    def bbmax(self) -> float:
+        return self._bounds()[1]
+
+    def _view(self):
+        from . import _abi
+
+        return _abi.HashGridView(self.points.data_ptr(), self.n_samples, self.bbmin, self.bbmax, self.resolution,
+                                 self.n_cells, self.cell_size.data_ptr(), self.cell_offset.data_ptr(),
+                                 self.sample_idx.data_ptr())
+
+    def _query_args(self, q, radius, what="query"):
+        """Validated (q, radius tensor, radius stride) of a query on a torch grid."""
+        from ._lib import MtxError
+
+        if not _torch_cuda(self.points):
+            raise MtxError("query needs torch CUDA tensors")
+        import torch
+
+        dev = self.points.device
+        if not isinstance(q, torch.Tensor) or not q.is_cuda:
+            raise MtxError(f"{what}: q: expected a torch CUDA tensor (a host tensor or array is not copied)")
+        if q.device != dev:
+            raise MtxError(f"{what}: q: on {q.device}, the grid is on {dev}")
+        if q.dtype != torch.float32:
+            raise MtxError(f"{what}: q: dtype {q.dtype}, expected torch.float32")
+        if q.dim() != 2 or q.shape[0] != 3:
+            raise MtxError(f"{what}: q: shape {tuple(q.shape)}, expected (3, N)")
+        if not q.is_contiguous():
+            raise MtxError(f"{what}: q: not contiguous (the kernels read whole planes; call .contiguous() yourself)")
+        m = q.shape[1]
+        if isinstance(radius, torch.Tensor):
+            if not radius.is_cuda or radius.device != dev:
+                raise MtxError(f"{what}: radius: on {radius.device}, the grid is on {dev}")
+            if radius.dtype != torch.float32:
+                raise MtxError(f"{what}: radius: dtype {radius.dtype}, expected torch.float32")
+            if tuple(radius.shape) != (m,):
+                raise MtxError(f"{what}: radius: shape {tuple(radius.shape)}, expected ({m},) or a float")
+            if not radius.is_contiguous():
+                raise MtxError(f"{what}: radius: not contiguous")
+            return q, radius, 1
+        return q, torch.full((1,), float(radius), dtype=torch.float32, device=dev), 0
+
+    def query(self, q, radius):
+        """The samples within `radius` (a float, or an (N,) tensor: one per
+        query) of each query point q (3, N): (count, offset, query_idx,
+        sample_idx) as int32 tensors, count and the exclusive offset per
+        query, the pairs grouped by query. A query's neighbours come in walk
+        order: grid cells ascending in cz, then cy, then cx, and ascending
+        sample index inside a grid cell. Sample j is a neighbour iff, in
+        fp32, (dx dx + dy dy) + dz dz <= r r with dx = p.x - q.x, ...; NaN in
+        q or r, or r < 0: none. One lane walks the cells a query's sphere can
+        touch; more than 4096 of them is an MtxError (build the grid with
+        resolution ~ extent / (2 r)). Torch CUDA tensors only."""
+        from . import _abi
+        from ._lib import MtxError
+        import ctypes as C
+
+        q, rad, stride = self._query_args(q, radius)
+        import torch
+
+        m, dev = q.shape[1], q.device
+        kw = {"dtype": torch.int32, "device": dev}
+        count = torch.zeros(m, **kw)
+        if m == 0 or self.n_samples == 0:
+            return count, torch.zeros(m, **kw), torch.empty(0, **kw), torch.empty(0, **kw)
+        ctx = _dev_ctx(q)
+        view = self._view()
+        check(lib().mtx_hashgrid_query_count_dev(ctx.handle, C.byref(view), q.data_ptr(), m, rad.data_ptr(), stride,
+                                                 count.data_ptr()), "mtx_hashgrid_query_count_dev")
+        total = int(count.sum(dtype=torch.int64).item())
+        if total > 2 ** 31 - 1:
+            raise MtxError(f"query: {total} pairs (more than 2^31 - 1); query fewer points or a smaller radius")
+        offset = prefix_sum(count, inclusive=False)
+        qi, si = torch.empty(total, **kw), torch.empty(total, **kw)
+        if total:
+            ctx = _dev_ctx(q)
+            check(lib().mtx_hashgrid_query_fill_dev(ctx.handle, C.byref(view), q.data_ptr(), m, rad.data_ptr(), stride,
+                                                    offset.data_ptr(), total, qi.data_ptr(), si.data_ptr()),
+                  "mtx_hashgrid_query_fill_dev")
+        return count, offset, qi, si
 
 
 def group_by(keys, n_keys: int, device: int | None = None):
