@@ -68,6 +68,16 @@ int unstage(mtx_ctx *c, std::initializer_list<Unstage> outs) {
 
 using namespace mtxh;
 
+// MTX_SHADE_CLASSES: "0" or "1". False (and the error set) for anything else.
+static bool shade_classes_knob(const char *e, uint32_t *out) {
+  if (!e || !(e[0] == '0' || e[0] == '1') || e[1]) {
+    mtx_set_error("MTX_SHADE_CLASSES=%s: 0 (the mixed shade loop) or 1 (class queues)", e ? e : "(null)");
+    return false;
+  }
+  *out = (uint32_t)(e[0] - '0');
+  return true;
+}
+
 // Every environment knob, with its clamp. Read once per context. False (and
 // the error set): a value that has no clamp to fall back on.
 static bool read_knobs(Knobs &k) {
@@ -91,6 +101,9 @@ static bool read_knobs(Knobs &k) {
     }
     k.trace_ring = (uint32_t)v;
   }
+  if (const char *e = getenv("MTX_SHADE_CLASSES")) {
+    if (!shade_classes_knob(e, &k.shade_classes)) return false;
+  }
   if (const char *e = getenv("MTX_XCD_CLAIM")) k.xcd_claim = atoi(e) != 0;
   if (const char *e = getenv("MTX_RS_FUSED")) k.rs_fused = atoi(e) ? 1u : 0u;
   if (const char *e = getenv("MTX_MEGA_PATHS")) k.mega_paths = (uint32_t)strtoul(e, nullptr, 0);
@@ -107,6 +120,12 @@ extern "C" {
 // count, or -1 in production builds.
 int mtx_diag_shade_stamps(unsigned long long *out) { return mtxd::shade_stamps(out); }
 
+// Diagnostic export (not in mtx.h): the mixed shade loop's class mix of an
+// MTX_DIAG_CLASSES build run with MTX_SHADE_CLASSES=0 (tools/shade_class_mix.py):
+// 16 bounces x (wave-steps holding 1, 2, 3 classes | entries of class 0, 1, 2);
+// returns the words per bounce, or -1 in production builds.
+int mtx_diag_shade_class_mix(unsigned long long *out) { return mtxd::shade_class_mix(out); }
+
 // Diagnostic export (not in mtx.h; needs no device): the LDS bytes of a
 // k_trace_closest block with rings of `ring` rays, for a tree deeper and
 // larger than the knobs ask for: out[0], and out[1] the stack entries it
@@ -119,6 +138,31 @@ int mtx_diag_trace_lds(uint32_t ring, uint32_t lds_stack, uint32_t lds_top, uint
   mtxd::split_trace_lds(s, ring);
   out[0] = (uint32_t)mtxd::ring_stack_bytes(s);
   out[1] = s.ring_lds_entries;
+  return MTX_OK;
+}
+
+// Diagnostic exports (not in mtx.h; need no device). The shading class of a
+// material type (mtx_core/shade_class.h):
+uint32_t mtx_diag_shade_class_of_type(uint32_t type) { return mtx::shade_class_of_type(type); }
+// how a context would read MTX_SHADE_CLASSES=`value` (out[0]: the knob), and
+// the dynamic LDS of a class-queue shade block with the ring's entries
+// (out[1] bytes, out[2] entries per ring, out[3] classes). MTX_E_ARG for a
+// value a context refuses.
+int mtx_diag_shade_classes_knob(const char *value, uint32_t *out) {
+  if (!out || !shade_classes_knob(value, &out[0])) return MTX_E_ARG;
+  out[1] = mtxd::shade_class_lds_bytes();
+  out[2] = mtxd::kClassRing;
+  out[3] = mtx::kShadeClasses;
+  return MTX_OK;
+}
+
+// Diagnostic export (not in mtx.h): the context's persistent shade grid and
+// its device's CUs (out[0] blocks, out[1] CUs): the grid is the occupancy
+// query's blocks per CU (with the class rings' LDS when they are on) x CUs.
+int mtx_diag_shade_grid(const mtx_ctx *c, uint32_t *out) {
+  if (!c || !out) return MTX_E_ARG;
+  out[0] = (uint32_t)c->shade_grid;
+  out[1] = (uint32_t)c->n_cu;
   return MTX_OK;
 }
 
@@ -154,7 +198,6 @@ int mtx_ctx_create(int hip_device, mtx_ctx **out) {
   // Persistent grids: every CU filled to the kernels' occupancy (the trace
   // grid is recomputed per scene: its LDS stack depends on the BVH depth).
   c->trace_grid = c->closest_grid = c->n_cu * 8;
-  c->shade_grid = c->n_cu * mtxd::shade_blocks_per_cu();
   {
     // a gfx950 workgroup may hold the CU's whole 160 KiB of LDS (the attribute
     // may report the 64 KiB that needs no opt-in; the kernels launch above it)
@@ -168,6 +211,8 @@ int mtx_ctx_create(int hip_device, mtx_ctx **out) {
     mtx_ctx_destroy(c);
     return MTX_E_ARG;
   }
+  // the class rings are the shade block's dynamic LDS: the occupancy query counts them
+  c->shade_grid = c->n_cu * mtxd::shade_blocks_per_cu(c->knobs.shade_classes != 0);
   *out = c;
   return MTX_OK;
 }

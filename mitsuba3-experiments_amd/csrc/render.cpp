@@ -289,7 +289,7 @@ void launch_bounce(mtx_ctx *c, const mtxd::WaveBuffers &b, const mtxd::ChunkPara
     ++*n_trace;
   }
   e = tm.begin(2, st);
-  mtxd::launch_shade(s, b, p, bounce, std::max(1, c->shade_grid / div), st);
+  mtxd::launch_shade(s, b, p, bounce, std::max(1, c->shade_grid / div), st, c->knobs.shade_classes != 0);
   tm.end(2, e, st);
   if (p.integrator != MTX_INT_PSSMLT_SIMPLE && p.integrator != MTX_INT_SIMPLE && !nerad_render &&
       !(nerad && bounce > 0)) {  // PSSMLT, simple and the nerad render trace no NEE rays

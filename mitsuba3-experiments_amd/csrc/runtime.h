@@ -116,6 +116,9 @@ struct Knobs {
   // k_trace_closest: prepared rays per wave in LDS (MTX_TRACE_RING: 0 = none, urefill refills; 16; 32). The
   // rings take their bytes from that kernel's LDS stack entries (wavefront.h split_trace_lds).
   uint32_t trace_ring = MTX_TRACE_RING;
+  // k_shade<path-mis / path>: class-uniform block steps from per-block LDS class queues (MTX_SHADE_CLASSES:
+  // 0 = the mixed loop, kept as the form the class queues are tested and measured against; 1)
+  uint32_t shade_classes = MTX_SHADE_CLASSES;
   uint32_t xcd_claim = 1;
   // ReSTIR GI: a band of at most this many paths runs its stage A in the
   // per-lane megakernel on one wavefront (MTX_MEGA_PATHS, 0 = off; default

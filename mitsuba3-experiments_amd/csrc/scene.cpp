@@ -8,6 +8,7 @@
 
 #include "runtime.h"
 #include "mtx_core/interaction.h"
+#include "mtx_core/shade_class.h"
 #include "scene_check.h"
 
 using namespace mtxh;
@@ -153,10 +154,10 @@ int mtx_scene_upload(mtx_ctx *c, const mtx_scene_desc *d) {
           r[24 + 2 * k + 1] = d->vuv[2 * (size_t)vi + 1];
         }
       }
-      // bits 8..12: shading class of the material (read by no kernel since
-      // the block-level material sort was measured slower and removed)
+      // bits 8..12: the material's type, textured and masked bits; k_shade
+      // reads its entries' shading class from them (mtx_core/shade_class.h)
       const mtx_material &m = d->materials[sh.material];
-      const uint32_t cls = 1u + ((m.type & 7u) << 2 | (m.tex >= 0 ? 2u : 0u) | ((m.flags & MTX_MF_MASK) ? 1u : 0u));
+      const uint32_t cls = mtx::shade_rec_class_bits(m.type, m.tex >= 0, (m.flags & MTX_MF_MASK) != 0);
       const uint32_t mat = sh.material, fl = use_n | use_uv | (cls << 8);
       const int32_t em = sh.emitter;
       memcpy(&r[3], &mat, 4);
@@ -343,6 +344,27 @@ int mtx_scene_update_vertices(mtx_ctx *c, const float *vpos, const float *vnorma
   hi.z = mtxd::refit_key_decode(h[mtxd::RF_HI + 2]);
   mtx::env_bsphere_box(lo, hi, c->scene.dev.env_center, &c->scene.dev.env_radius);
   c->geometry_moved();  // the ReSTIR GI reservoirs are kept (runtime.h RestirState)
+  return MTX_OK;
+}
+
+// Diagnostic export (not in mtx.h; needs no device): the shading class of
+// every triangle of a scene description, read back from the flag word the
+// record builder of mtx_scene_upload writes (out: n_tris bytes).
+int mtx_diag_shade_classes(const mtx_scene_desc *d, uint8_t *out) {
+  if (!d || !out || !d->tri_shape || !d->shapes || !d->materials) {
+    mtx_set_error("mtx_diag_shade_classes: null argument");
+    return MTX_E_ARG;
+  }
+  for (uint32_t t = 0; t < d->n_tris; ++t) {
+    const uint32_t sh = d->tri_shape[t];
+    if (sh >= d->n_shapes || d->shapes[sh].material >= d->n_materials) {
+      mtx_set_error("mtx_diag_shade_classes: triangle %u: shape or material out of range", t);
+      return MTX_E_ARG;
+    }
+    const mtx_material &m = d->materials[d->shapes[sh].material];
+    const uint32_t fl = mtx::shade_rec_class_bits(m.type, m.tex >= 0, (m.flags & MTX_MF_MASK) != 0) << 8;
+    out[t] = (uint8_t)mtx::shade_class_of_rec(fl);
+  }
   return MTX_OK;
 }
 

@@ -48,11 +48,62 @@ __global__ void k_raygen_rays(DevScene s, WaveBuffers b, ChunkParams p, const fl
 __device__ unsigned long long g_shade_stamps[kStampSegs + 2];  // the stamp sums (shade_dev.h Stamps)
 #endif
 
+// Diagnostic build only (MTX_DIAG_CLASSES=1, tools/shade_class_mix.py): what
+// the waves of the mixed loop hold. Per bounce: the wave-steps with 1, 2 and
+// 3 shading classes among their entries, then the entries of each class.
+#ifndef MTX_DIAG_CLASSES
+#define MTX_DIAG_CLASSES 0
+#endif
+#if MTX_DIAG_CLASSES
+constexpr uint32_t kMixBounces = 16, kMixWords = 2 * mtx::kShadeClasses;
+__device__ unsigned long long g_class_mix[kMixBounces][kMixWords];
+__device__ __forceinline__ void class_mix_count(const DevScene &s, uint32_t bounce, bool valid, const float4 h) {
+  const uint32_t prim = __float_as_uint(h.y);
+  uint32_t cw = 0;
+  if (valid && prim != 0xffffffffu) cw = __float_as_uint(s.shade_rec[8 * (size_t)prim + 2].w);
+  const uint32_t cls = mtx::shade_class_of_rec(cw);
+  uint32_t held = 0, n[mtx::kShadeClasses];
+  for (uint32_t k = 0; k < mtx::kShadeClasses; ++k) {
+    n[k] = (uint32_t)__popcll(__ballot(valid && cls == k));
+    held += n[k] ? 1u : 0u;
+  }
+  if ((threadIdx.x & 63u) == 0 && held && bounce < kMixBounces) {
+    atomicAdd(&g_class_mix[bounce][held - 1], 1ull);
+    for (uint32_t k = 0; k < mtx::kShadeClasses; ++k)
+      atomicAdd(&g_class_mix[bounce][mtx::kShadeClasses + k], (unsigned long long)n[k]);
+  }
+}
+#endif
+
 // The persistent shade loop of a bounce: k_shade's body. CAM: bounce 0 of a
 // cam0 chunk (k_shade_cam), bounce_ is 0.
-template <int INT, bool CAM>
+//
+// CLS (path-mis and path; the launch carries shade_class_lds_bytes() of
+// dynamic LDS): the same bounce with class-uniform block steps. A block sorts
+// its grid-stride queue windows into one LDS ring per shading class
+// (mtx_core/shade_class.h) and shades 256 entries of one class at a time, so
+// a wave's lanes run one case of the BSDF switch; no pass over HBM is added.
+// Per iteration: while no ring holds a full step and the queue has windows
+// left, the next window is ingested (a lane's rank in its ring: one ballot
+// per class, mbcnt and the waves' counts through LDS, so a ring stays in
+// queue order), which always fits: no ring holds 256, and a ring has room for
+// 512. Then the oldest 256 entries of the fullest ring are shaded, lane t
+// taking entry head + t; once the queue is exhausted the rings' remainders
+// are shaded packed, mixed as without CLS. The step itself is the same; path
+// state is read at the entry's own queue position, survivors get consecutive
+// append slots. The class of a window's entries comes from flag word 11 of
+// their shading records; that load also is the L2 warm-up of the record
+// (io.warm without CLS). A window loads ahead of its ingest: queue entries
+// and hit records behind the ingest before, the class words behind the shade
+// step before (6 registers live across a step; loaded at the ingest instead
+// the bench step takes 135.8 against 134.2 ms). The ingest is an inner loop
+// on purpose: as a branch of one loop with the shade step, ShadeIO's
+// conditionally written fields became loop-carried copies and k_shade<2>
+// spilled 42 VGPRs at its 168-VGPR budget.
+template <int INT, bool CAM, bool CLS = false>
 __device__ __forceinline__ void shade_loop(const DevScene &s, const WaveBuffers &b, const ChunkParams &p,
                                            uint32_t bounce_) {
+  static_assert(!CLS || (shade_has_classes(INT) && !CAM), "class queues: k_shade of path-mis and path");
   const uint32_t bounce = CAM ? 0u : bounce_;
   const SceneView sv = make_view(s);
   const uint32_t count = b.counters[4 * bounce + 0];
@@ -69,7 +120,8 @@ __device__ __forceinline__ void shade_loop(const DevScene &s, const WaveBuffers 
   // software pipeline over the persistent loop: the next step's queue entry
   // loads during this step, its hit record before this step's appends. Hit
   // records are stored by queue position (ClosestSrc), so they load
-  // coalesced and in parallel with the queue entry.
+  // coalesced and in parallel with the queue entry. (CLS: path / h are the
+  // window to ingest next, at nbase.)
   uint32_t path = 0;
   float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
   // an identity bounce-0 queue is not stored: position i is path i
@@ -79,45 +131,170 @@ __device__ __forceinline__ void shade_loop(const DevScene &s, const WaveBuffers 
     path = ident ? i0 : ld_stream<kNtQueue>(in_q + i0);
     h = ld_stream<kNtShade>(b.hit + i0);
   }
+  // CLS: the rings, [class][kClassRing] hit records, then [class][kClassRing]
+  // position | path; an ingest's entries per wave and class; the block-uniform
+  // ring state (scalar registers); the class words of the window at nbase
+  constexpr uint32_t kC = mtx::kShadeClasses, kW = kShadeBlock / 64, kMask = kClassRing - 1;
+  static_assert((kClassRing & kMask) == 0 && kClassRing >= 2 * kShadeBlock, "a ring holds two block steps");
+  static_assert(kClassEntryBytes == sizeof(float4) + sizeof(uint2), "ring entry: hit record | position, path");
+  extern __shared__ float4 class_lds[];
+  float4 *ring_h = class_lds;
+  uint2 *ring_ip = reinterpret_cast<uint2 *>(class_lds + kC * kClassRing);
+  __shared__ uint32_t class_wcnt[CLS ? kW : 1][kC];
+  uint32_t head[kC] = {}, fill[kC] = {};
+  uint32_t nbase = blockIdx.x * kShadeBlock, cw = 0;
+  bool cw_due = CLS && nbase < count;  // the window's class words are not loaded yet
+  auto load_class_word = [&]() {
+    const uint32_t pn = __float_as_uint(h.y);
+    cw = 0;  // a miss or a lane past the queue's end: no record, class 0
+    if (nbase + threadIdx.x < count && pn != 0xffffffffu) cw = __float_as_uint(s.shade_rec[8 * (size_t)pn + 2].w);
+    cw_due = false;
+  };
 
   Stamps stp{};
   MTX_STAMP_BEGIN(stp);
-  for (uint32_t base = blockIdx.x * kShadeBlock; base < count; base += stride, parity ^= 1u) {
-    const uint32_t i = base + threadIdx.x;
-    const uint32_t inext = i + stride;
-    uint32_t path_n = 0;
-    if (inext < count) path_n = ident ? inext : ld_stream<kNtQueue>(in_q + inext);
-    // the next step's hit record, and from it the address of the shading
-    // record that step will read: shade_path touches one word of it (L2 warm-up)
-    float4 hn = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (inext < count) hn = b.hit[inext];
-    const uint32_t pn = __float_as_uint(hn.y);
-    const float4 *wp = (inext < count && pn != 0xffffffffu) ? s.shade_rec + 8 * (size_t)pn : nullptr;
+  for (uint32_t base = blockIdx.x * kShadeBlock; CLS || base < count; base += CLS ? 0u : stride, parity ^= 1u) {
+    uint32_t i = base + threadIdx.x, path_s = path, path_n = 0;
+    float4 h_s = h, hn = make_float4(0.f, 0.f, 0.f, 0.f);
+    bool valid = i < count;
+    const float4 *wp = nullptr;
+    if constexpr (!CLS) {
+      const uint32_t inext = i + stride;
+      if (inext < count) path_n = ident ? inext : ld_stream<kNtQueue>(in_q + inext);
+      // the next step's hit record, and from it the address of the shading
+      // record that step will read: shade_path touches one word of it (L2 warm-up)
+      if (inext < count) hn = b.hit[inext];
+      const uint32_t pn = __float_as_uint(hn.y);
+      wp = (inext < count && pn != 0xffffffffu) ? s.shade_rec + 8 * (size_t)pn : nullptr;
+    } else {
+      const uint32_t wave = threadIdx.x >> 6;
+      uint32_t c, most, held;  // the fullest ring, its entries, all rings' entries
+      for (;;) {
+        c = 0;
+        most = held = fill[0];
+#pragma unroll
+        for (uint32_t k = 1; k < kC; ++k) {
+          if (fill[k] > most) {
+            most = fill[k];
+            c = k;
+          }
+          held += fill[k];
+        }
+        if (most >= (uint32_t)kShadeBlock || nbase >= count) break;
+        // ---- ingest the window at nbase
+        if (cw_due) load_class_word();
+        const uint32_t i_n = nbase + threadIdx.x;
+        const bool in = i_n < count;
+        const uint32_t cls = mtx::shade_class_of_rec(cw);
+        uint64_t m[kC];
+#pragma unroll
+        for (uint32_t k = 0; k < kC; ++k) m[k] = __ballot(in && cls == k);
+        if ((threadIdx.x & 63u) == 0) {
+#pragma unroll
+          for (uint32_t k = 0; k < kC; ++k) class_wcnt[wave][k] = (uint32_t)__popcll(m[k]);
+        }
+        __syncthreads();
+        uint32_t slot = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kC; ++k) {
+          uint32_t before = 0, total = 0;
+#pragma unroll
+          for (uint32_t w = 0; w < kW; ++w) {
+            const uint32_t n = __builtin_amdgcn_readfirstlane(class_wcnt[w][k]);
+            if (w < wave) before += n;
+            total += n;
+          }
+          const uint32_t rank = before + __builtin_amdgcn_mbcnt_hi((uint32_t)(m[k] >> 32),
+                                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)m[k], 0u));
+          if (cls == k) slot = k * kClassRing + ((head[k] + fill[k] + rank) & kMask);
+          fill[k] += total;
+        }
+        if (in) {
+          ring_h[slot] = h;
+          ring_ip[slot] = make_uint2(i_n, path);
+        }
+        nbase += stride;
+        if (nbase + threadIdx.x < count) {  // the next window, with the policies of the mixed loop's next step
+          path = ident ? nbase + threadIdx.x : ld_stream<kNtQueue>(in_q + nbase + threadIdx.x);
+          h = b.hit[nbase + threadIdx.x];
+        }
+        cw_due = nbase < count;
+        __syncthreads();  // the entries are in the rings; class_wcnt is free for the next ingest
+      }
+      if (held == 0) break;
+      // ---- this step's entries: 256 of ring c, or (the queue is exhausted) the rings' remainders packed
+      valid = false;
+      if (most >= (uint32_t)kShadeBlock) {
+        uint32_t hc = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kC; ++k)  // head[] and fill[] stay registers: no dynamic index
+          if (c == k) {
+            hc = head[k];
+            head[k] = (head[k] + kShadeBlock) & kMask;
+            fill[k] -= kShadeBlock;
+          }
+        const uint32_t slot = c * kClassRing + ((hc + threadIdx.x) & kMask);
+        const uint2 ip = ring_ip[slot];
+        h_s = ring_h[slot];
+        i = ip.x;
+        path_s = ip.y;
+        valid = true;
+      } else {
+        uint32_t t = threadIdx.x, room = kShadeBlock;
+#pragma unroll
+        for (uint32_t k = 0; k < kC; ++k) {
+          const uint32_t take = fill[k] < room ? fill[k] : room;  // uniform
+          if (!valid && t < take) {
+            const uint32_t slot = k * kClassRing + ((head[k] + t) & kMask);
+            const uint2 ip = ring_ip[slot];
+            h_s = ring_h[slot];
+            i = ip.x;
+            path_s = ip.y;
+            valid = true;
+          }
+          t -= take;  // wraps for the lanes that took an entry: valid keeps them out
+          head[k] = (head[k] + take) & kMask;
+          fill[k] -= take;
+          room -= take;
+        }
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < kC; ++k) {
+        head[k] = __builtin_amdgcn_readfirstlane(head[k]);
+        fill[k] = __builtin_amdgcn_readfirstlane(fill[k]);
+      }
+    }
     ShadeIO io;
     io.reset();
     MTX_STAMP_STEP(stp);
     io.st = stp;
     bool cont = false;
-    const bool valid = i < count;
+#if MTX_DIAG_CLASSES
+    if constexpr (!CAM && !CLS && shade_has_classes(INT)) class_mix_count(s, bounce, valid, h_s);
+#endif
     if (valid) {
       if constexpr (INT == MTX_INT_PSSMLT_SIMPLE)
-        cont = shade_pssmlt(s, sv, b, p, bounce, path, i, h, io);
+        cont = shade_pssmlt(s, sv, b, p, bounce, path_s, i, h_s, io);
       else if constexpr (INT == MTX_INT_SIMPLE)
-        cont = shade_simple<CAM>(s, sv, b, p, bounce, path, i, h, io);
+        cont = shade_simple<CAM>(s, sv, b, p, bounce, path_s, i, h_s, io);
       else if constexpr (INT == MTX_INT_PSSMLT_PATH)
-        cont = shade_pssmlt_path(s, sv, b, p, bounce, path, i, h, io);
+        cont = shade_pssmlt_path(s, sv, b, p, bounce, path_s, i, h_s, io);
       else if constexpr (INT == MTX_INT_NERAD_RHS)
-        cont = shade_nerad<false>(s, sv, b, bounce, path, i, h, io);
+        cont = shade_nerad<false>(s, sv, b, bounce, path_s, i, h_s, io);
       else if constexpr (INT == MTX_INT_NERAD)
-        cont = shade_nerad<true>(s, sv, b, bounce, path, i, h, io);
+        cont = shade_nerad<true>(s, sv, b, bounce, path_s, i, h_s, io);
       else
-        cont = shade_path<INT, CAM>(s, sv, b, p, bounce, path, i, h, io, wp);
+        cont = shade_path<INT, CAM>(s, sv, b, p, bounce, path_s, i, h_s, io, wp);
     }
     (void)wp;
-    const uint32_t path_c = path;
-    path = path_n;
-    h = hn;
-    asm volatile("" ::"v"(io.warm));  // the warm-up load completes in this iteration
+    const uint32_t path_c = path_s;
+    if constexpr (!CLS) {
+      path = path_n;
+      h = hn;
+      asm volatile("" ::"v"(io.warm));  // the warm-up load completes in this iteration
+    } else {
+      if (cw_due) load_class_word();  // the window's hit records arrived during the step
+    }
     stp = io.st;
 
     uint32_t slot, sslot;
@@ -173,8 +350,16 @@ __device__ __forceinline__ void shade_loop(const DevScene &s, const WaveBuffers 
 #endif
 }
 
+// k_shade: the production kernel of every integrator (path-mis and path
+// with class queues). k_shade_mixed: the mixed loop of those two, the form
+// MTX_SHADE_CLASSES=0 launches.
 template <int INT>
 __global__ __launch_bounds__(kShadeBlock, kShadeMinBlocks) void k_shade(DevScene s, WaveBuffers b, ChunkParams p, uint32_t bounce) {
+  shade_loop<INT, false, shade_has_classes(INT)>(s, b, p, bounce);
+}
+template <int INT>
+__global__ __launch_bounds__(kShadeBlock, kShadeMinBlocks) void k_shade_mixed(DevScene s, WaveBuffers b, ChunkParams p, uint32_t bounce) {
+  static_assert(shade_has_classes(INT), "k_shade_mixed: the integrators whose k_shade runs class queues");
   shade_loop<INT, false>(s, b, p, bounce);
 }
 // Bounce 0 of a cam0 chunk (path, path-mis, nrc, simple): the camera sample
@@ -336,7 +521,8 @@ void launch_raygen_rays(const DevScene &s, const WaveBuffers &b, const ChunkPara
                      rng_skip);
 }
 void launch_shade(const DevScene &s, const WaveBuffers &b, const ChunkParams &p, uint32_t bounce, int grid,
-                  hipStream_t st) {
+                  hipStream_t st, bool classes) {
+  const size_t rings = shade_class_lds_bytes();
   if (bounce == 0 && p.cam0) {  // no stored raygen (mtx_render sets cam0 for these four only)
     switch (p.integrator) {
       case MTX_INT_PATH:
@@ -355,7 +541,10 @@ void launch_shade(const DevScene &s, const WaveBuffers &b, const ChunkParams &p,
   }
   switch (p.integrator) {
     case MTX_INT_PATH:
-      hipLaunchKernelGGL(k_shade<MTX_INT_PATH>, dim3(grid), dim3(kShadeBlock), 0, st, s, b, p, bounce);
+      if (classes)
+        hipLaunchKernelGGL(k_shade<MTX_INT_PATH>, dim3(grid), dim3(kShadeBlock), rings, st, s, b, p, bounce);
+      else
+        hipLaunchKernelGGL(k_shade_mixed<MTX_INT_PATH>, dim3(grid), dim3(kShadeBlock), 0, st, s, b, p, bounce);
       break;
     case MTX_INT_NRC:
       hipLaunchKernelGGL(k_shade<MTX_INT_NRC>, dim3(grid), dim3(kShadeBlock), 0, st, s, b, p, bounce);
@@ -376,7 +565,10 @@ void launch_shade(const DevScene &s, const WaveBuffers &b, const ChunkParams &p,
       hipLaunchKernelGGL(k_shade<MTX_INT_NERAD>, dim3(grid), dim3(kShadeBlock), 0, st, s, b, p, bounce);
       break;
     default:
-      hipLaunchKernelGGL(k_shade<MTX_INT_PATH_MIS>, dim3(grid), dim3(kShadeBlock), 0, st, s, b, p, bounce);
+      if (classes)
+        hipLaunchKernelGGL(k_shade<MTX_INT_PATH_MIS>, dim3(grid), dim3(kShadeBlock), rings, st, s, b, p, bounce);
+      else
+        hipLaunchKernelGGL(k_shade_mixed<MTX_INT_PATH_MIS>, dim3(grid), dim3(kShadeBlock), 0, st, s, b, p, bounce);
   }
 }
 // MTX_DIAG_STAMPS builds: read (and zero) the shade stamp sums; -1 otherwise.
@@ -394,10 +586,29 @@ int shade_stamps(unsigned long long *out) {
   return -1;
 #endif
 }
-int shade_blocks_per_cu() {
+// MTX_DIAG_CLASSES builds: read (and zero) the class-mix counts, kMixBounces rows
+// of kMixWords; returns kMixWords, or -1 otherwise.
+int shade_class_mix(unsigned long long *out) {
+#if MTX_DIAG_CLASSES
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_class_mix), sizeof(unsigned long long) * kMixBounces * kMixWords) !=
+      hipSuccess)
+    return -1;
+  unsigned long long z[kMixBounces * kMixWords] = {};
+  if (hipMemcpyToSymbol(HIP_SYMBOL(g_class_mix), z, sizeof(z)) != hipSuccess) return -1;
+  return (int)kMixWords;
+#else
+  (void)out;
+  return -1;
+#endif
+}
+int shade_blocks_per_cu(bool classes) {
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_shade<MTX_INT_PATH_MIS>, kShadeBlock, 0) != hipSuccess ||
-      nb <= 0)
+  const hipError_t e =
+      classes ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_shade<MTX_INT_PATH_MIS>, kShadeBlock,
+                                                             shade_class_lds_bytes())
+              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_shade_mixed<MTX_INT_PATH_MIS>, kShadeBlock, 0);
+  if (e != hipSuccess || nb <= 0)
     nb = 2;
   return nb;
 }

@@ -30,6 +30,7 @@
 
 #include "mtx.h"
 #include "mtx_core/nerad.h"
+#include "mtx_core/shade_class.h"
 
 namespace mtxd {
 
@@ -70,6 +71,20 @@ static_assert(ring_size_ok(MTX_TRACE_RING), "MTX_TRACE_RING: 0, 16 or 32");
 constexpr uint32_t kTraceLds = 20 * 1024;  // LDS of a trace block
 constexpr uint32_t kRingWords = 14;        // TraceRay | queue position
 constexpr uint32_t ring_bytes(uint32_t R) { return R * 4u * kRingWords * (kTraceBlock / 64u); }
+// Class queues of k_shade<path-mis / path> (shade.hip shade_loop<INT, CAM, CLS>,
+// MTX_SHADE_CLASSES env: 0 = the mixed loop): one ring per shading class
+// (mtx_core/shade_class.h) in each block's dynamic LDS; an entry is the
+// queue position, the path index and the 16-B hit record. Two block steps
+// per ring: a window always fits while no ring holds a full step.
+#ifndef MTX_SHADE_CLASSES
+#define MTX_SHADE_CLASSES 1
+#endif
+constexpr uint32_t kClassRing = 2 * kShadeBlock;
+constexpr uint32_t kClassEntryBytes = 24;
+constexpr uint32_t shade_class_lds_bytes() { return mtx::kShadeClasses * kClassRing * kClassEntryBytes; }
+constexpr bool shade_has_classes(int integrator) {
+  return integrator == MTX_INT_PATH_MIS || integrator == MTX_INT_PATH;
+}
 #ifndef MTX_CACHE_SORT
 #define MTX_CACHE_SORT 2  // NRC cache query order (render.cpp run_cache): 0 as appended, 1 Morton sort, 2 region x XCD
 #endif
@@ -285,7 +300,7 @@ struct ChunkParams {
 // -------- launch wrappers (trace.hip, shade.hip, mega.hip, film.hip) --------
 int trace_blocks_per_cu(const DevScene &s);    // any-hit kernels
 int closest_blocks_per_cu(const DevScene &s);  // k_trace_closest
-int shade_blocks_per_cu();
+int shade_blocks_per_cu(bool classes);  // k_shade<path-mis>, with its class rings or as the mixed loop
 int mega_blocks_per_cu(const DevScene &s);
 // all bounces of a short path-mis / path wavefront in one kernel (k_path_mega)
 void launch_path_mega(const DevScene &s, const WaveBuffers &b, const ChunkParams &p, int grid, hipStream_t st);
@@ -293,6 +308,7 @@ void launch_path_mega(const DevScene &s, const WaveBuffers &b, const ChunkParams
 void launch_rs_stage_a(const DevScene &s, const WaveBuffers &b, const ChunkParams &p, const RestirBuffers &r,
                        int grid, hipStream_t st);
 int shade_stamps(unsigned long long *out);  // diagnostic builds (MTX_DIAG_STAMPS)
+int shade_class_mix(unsigned long long *out);  // diagnostic builds (MTX_DIAG_CLASSES): 16 bounces x 6 counts
 void launch_raygen_camera(const DevScene &s, const WaveBuffers &b, const ChunkParams &p, hipStream_t st);
 void launch_raygen_rays(const DevScene &s, const WaveBuffers &b, const ChunkParams &p, const float *rays,
                         const uint32_t *lanes, uint32_t rng_skip, hipStream_t st);
@@ -302,8 +318,9 @@ void launch_trace_closest(const DevScene &s, const WaveBuffers &b, uint32_t boun
 void launch_trace_camera(const DevScene &s, const WaveBuffers &b, const ChunkParams &p, int grid, hipStream_t st);
 void launch_trace_shadow(const DevScene &s, const WaveBuffers &b, uint32_t bounce, uint32_t stats, int grid,
                          hipStream_t st);
+// classes: path-mis / path bounces run the class-queue loop (the other integrators have the mixed loop only)
 void launch_shade(const DevScene &s, const WaveBuffers &b, const ChunkParams &p, uint32_t bounce, int grid,
-                  hipStream_t st);
+                  hipStream_t st, bool classes);
 void launch_film_src(const WaveBuffers &b, const ChunkParams &p, float4 *contrib, hipStream_t st);
 void launch_film_gather(const float4 *contrib, float4 *film, uint32_t width, uint32_t y0, uint32_t y1,
                         uint32_t nslots, uint32_t slot_mask, uint32_t rfilter, hipStream_t st);
